@@ -2,6 +2,7 @@
 """Benchmark: batched SRBD OCP-QP solves/sec on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--batch B]
+                  [--dump-outputs DIR] [--full]
 
 A "step" is one solve of the whole per-rank batch (one C-ABI call, inputs
 already resident in HBM).  Every rank generates its own shard of synthetic
@@ -9,6 +10,11 @@ SRBD QPs from seed + global QP index, so the data path has no
 collective; `value` = QPs solved by all ranks / max-over-ranks wall time
 ("scaling": "weak").  After the timed region the solutions are gathered to
 rank 0 over RCCL (BASELINE config 4) and that rate is reported separately.
+
+A plain run does only what `value` needs: set up, warm up, time the K steps,
+write the outputs (--dump-outputs) and print the line.  --full adds every other
+measurement beside it (CPU baselines, the IPM workloads, the SQP pipeline, the
+host-buffer path, the reference's call pattern); the --no-* options narrow it.
 
 Rank 0 prints ONE JSON line on stdout; progress goes to stderr.
 """
@@ -157,6 +163,35 @@ def gather_solutions(pkg, sol_t, world, rank, cpu_staged=False):
     return pkg.dist.gather_to_root(payload, world, rank)
 
 
+DUMP_MAX_BYTES = 60 * 2 ** 20  # --dump-outputs: under 64 MB in all
+
+
+def dump_outputs(out_dir, sol_t, rank, world):
+    """--dump-outputs: what the last timed step left in the caller's solution
+    buffers (x, u, pi in the workload's dtype; status and iter as float32) as
+    DIR/<name>.npy (ranks of an N > 1 run: <name>_rank<r>.npy, each its own shard).
+    A shard too large for the size limit is written as a fixed sample of its QPs
+    (the same sorted indices for every run of the same batch)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    batch = int(sol_t["status"].shape[0])
+    per_qp = sum(v[0].numel() * (4 if k in ("status", "iter") else v.element_size())
+                 for k, v in sol_t.items())
+    n = min(batch, DUMP_MAX_BYTES // per_qp)
+    idx = None
+    if n < batch:
+        idx = np.sort(np.random.default_rng(20240).choice(batch, size=n, replace=False))
+    for k, v in sol_t.items():
+        a = v.cpu().numpy()
+        if idx is not None:
+            a = a[idx]
+        if k in ("status", "iter"):
+            a = a.astype(np.float32)
+        np.save(out_dir / (f"{k}.npy" if world == 1 else f"{k}_rank{rank}.npy"), np.ascontiguousarray(a))
+    log(f"[rank {rank}] outputs of the last timed step written to {out_dir} "
+        f"({n} of {batch} QPs)")
+
+
 def baseline_config_name(workload, global_batch, world):
     """Which BASELINE.json config a run measures (None if it is none of them)."""
     if workload == "unconstr_n20" and global_batch == 262144 and world == 8:
@@ -227,6 +262,13 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="QPs over all ranks, split evenly (strong scaling; BASELINE config 4 is "
                          "--gpus 8 --global-batch 262144)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solution arrays of the last step "
+                         "(x, u, pi, status, iter) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside `value`: CPU baselines, the IPM "
+                         "workloads, the SQP pipeline, the host-buffer path and the reference's "
+                         "call pattern (each can be switched off by its --no-* option)")
     ap.add_argument("--cpu-pool", type=int, default=4096, help="QPs in the cpu_baseline sample")
     ap.add_argument("--seed", type=int, default=1003)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="cpu_baseline budget")
@@ -261,6 +303,8 @@ def main():
         F32_SETTINGS["mode"] = args.mode
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: start the N ranks ourselves, before anything touches the GPU
@@ -358,20 +402,23 @@ def main():
     n_ok = int((status == 0).sum())
     log(f"[rank {rank}] wall {t_wall * 1e3:.2f} ms for {args.steps} steps, kernel avg {kernel_ms:.3f} ms, "
         f"success {n_ok}/{batch}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sol_t, rank, world)
 
     # ---- the whole SQP iteration on the device (secondary; not `value`) ----
     pipeline = None
-    if not args.no_pipeline and dtype == "f64" and not stage_major:
+    if args.full and not args.no_pipeline and dtype == "f64" and not stage_major:
         pipeline = sqp_pipeline(pkg, h, N, constraints, batch, xs_np, us_np, x0_np, device, settings)
 
     # ---- host buffers in, host buffers out (secondary; PCIe-inclusive, not `value`) ----
     host = None
-    if not args.no_host_path and not stage_major and rank == 0:
+    if args.full and not args.no_host_path and not stage_major and rank == 0:
         host = host_path(capi, h, dt, batch, N, settings, dtype)
 
     # ---- the reference's construct-solve-destroy call pattern, batch 1 (secondary) ----
     pattern = None
-    if not args.no_host_path and rank == 0 and world == 1 and args.workload == DEFAULT_WORKLOAD:
+    if (args.full and not args.no_host_path and rank == 0 and world == 1
+            and args.workload == DEFAULT_WORKLOAD):
         pattern = call_pattern(pkg, args.seed)
 
     # ---- solution gather to rank 0 over RCCL (BASELINE config 4) ----
@@ -400,7 +447,7 @@ def main():
     flops_qp = alg_flops_per_qp(N)
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
         qp, x0 = make_cpu_sample(pkg, N, constraints, min(batch, args.cpu_pool), rank, batch, args.seed)
         cpu = cpu_baseline(pkg, qp, x0, settings_dict(settings), args.cpu_seconds)
         if dtype == "f32":
@@ -408,7 +455,7 @@ def main():
 
     # ---- the IPM configurations (BASELINE configs 3 and 5) beside the default line ----
     secondary = None
-    if not args.no_secondary and world == 1 and args.workload == DEFAULT_WORKLOAD:
+    if args.full and not args.no_secondary and world == 1 and args.workload == DEFAULT_WORKLOAD:
         del h, dt, data, sol, sol_t
         torch.cuda.empty_cache()
         secondary = {w: secondary_workload(pkg, capi, w, device, args.seed)

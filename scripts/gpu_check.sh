@@ -5,7 +5,8 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${1:-r01}
-BENCH_ARGS=${BENCH_ARGS:-"--steps 10 --warmup 2"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --steps 10 --warmup 2"}
+PROF_ARGS="--full $PROF_ARGS"
 timeout -k 10 900 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS} > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc"; tail -5 gpurun_out/pytest_gpu.log
 if [ $rc -gt 1 ] && [ $rc -ne 5 ]; then exit $rc; fi

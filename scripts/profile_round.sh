@@ -19,5 +19,5 @@ for W in unconstr_n20 box_u_n20 cone_n40_f32; do
   cp profiles/$TAG/${W}_* $OUT/ || exit $?
 done
 cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log || exit $?
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log || exit $?
 echo done
