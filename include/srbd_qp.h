@@ -33,6 +33,8 @@
  *   min  sum_k 1/2 x'Q x + u'S x + 1/2 u'R u + q'x + r'u
  *   s.t. x[k+1] = A x[k] + B u[k] + b,  x[0] = x0,
  *        lbu <= u <= ubu, lbx <= x <= ubx (k >= 1), lg <= C x + D u <= ug.
+ * Box bounds may be soft (HPIPM's Zl / Zu / zl / zu / idxs / lls / lus):
+ * srbd_qp_solve_soft_f64 below; general rows are hard.
  * x0 is embedded like hpipm-cpp does it (nx[0] = nbx[0] = 0,
  * ocp_qp_ipm_solver.cpp:128-130): box-x bounds and C at stage 0 are ignored.
  *
@@ -324,6 +326,50 @@ int srbd_qp_solve_f32(srbd_qp_handle h, int batch, const srbd_qp_settings* setti
                       void* stream);
 int srbd_qp_solve_host_f32(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
                            const srbd_qp_data_f32* data, const srbd_qp_solution_f32* sol);
+
+/* ------------------------------------------------------------------------
+ * Soft box constraints (soft, additive to ABI 12): HPIPM's OCP-QP slack
+ * variables (Zl / Zu / zl / zu / idxs / lls / lus, nsbx / nsbu) on box bounds.
+ * A box bound marked soft gets a slack on each active side,
+ *     lbx - sl <= x <= ubx + su,   sl >= lls,  su >= lus,
+ * penalised in the cost by 1/2 Zl sl^2 + zl sl + 1/2 Zu su^2 + zu su (the same
+ * for u), so a bound that x0 or a disturbance violates costs instead of making
+ * the QP infeasible.  Dense per variable like the box masks: soft_* = 1 marks
+ * the variable's box as soft; a side whose mask is 0 has no slack.  Z is the
+ * diagonal of HPIPM's Zl / Zu (stored there as a vector too).
+ * Caller's contract (device data, not checked): Z >= 0, z >= 0, Z + z > 0 on
+ * every active soft side, and lls / lus finite.
+ * (soft, additive to ABI 12)                                                 */
+typedef struct srbd_qp_soft_f64 {      /* dense per variable, like the box masks            */
+  const double *soft_u, *soft_x;       /* [batch][N][nu], [batch][N+1][nx]: 1 = this box is soft (NULL: none) */
+  const double *Zl_u, *Zu_u, *zl_u, *zu_u;   /* [batch][N][nu]   diagonal Z (HPIPM stores Z as a vector) */
+  const double *Zl_x, *Zu_x, *zl_x, *zu_x;   /* [batch][N+1][nx] stage 0 ignored, like lbx   */
+  const double *lls_u, *lus_u, *lls_x, *lus_x; /* slack lower bounds, NULL = 0                */
+} srbd_qp_soft_f64;
+/* optional slack outputs, shaped like the bounds (any may be NULL); 0 where the
+ * variable is not soft or the side is masked.  (soft, additive to ABI 12)     */
+typedef struct srbd_qp_slack_f64 { double *sl_u, *su_u, *sl_x, *su_x; } srbd_qp_slack_f64;
+
+/* srbd_qp_solve_f64 with soft boxes: device memory, asynchronous on `stream`.
+ * soft->soft_u needs a handle with has_box_u (and Zl_u, Zu_u, zl_u, zu_u),
+ * soft->soft_x one with has_box_x (and Zl_x ... zu_x); `slack` may be NULL.
+ * Always runs the batched fp64 kernels (never the latency IPM).  Rejected:
+ * ng > 0 (SRBD_QP_EDIM: soft general rows are not built); mode Balance /
+ * Robust, f32_iters and f64_rescue (SRBD_QP_ESETTINGS: the refinement and the
+ * fp32 kernels do not carry the slack rows).  warm_start = 1 warms x / u only;
+ * the slacks always start cold.  iter, res and obj count the slack rows and
+ * the penalty.  The slack state lives in a buffer the handle allocates on
+ * first use (srbd_qp_memory_bytes counts it).  (soft, additive to ABI 12)    */
+int srbd_qp_solve_soft_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
+                           const srbd_qp_data_f64* data, const srbd_qp_soft_f64* soft,
+                           const srbd_qp_solution_f64* sol, const srbd_qp_slack_f64* slack,
+                           void* stream);
+/* The same from host buffers: copies to the device, solves, copies back, waits
+ * (a per-call device buffer; Riccati outputs and stat are not returned: pass
+ * them NULL).  (soft, additive to ABI 12)                                     */
+int srbd_qp_solve_soft_host_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
+                                const srbd_qp_data_f64* data, const srbd_qp_soft_f64* soft,
+                                const srbd_qp_solution_f64* sol, const srbd_qp_slack_f64* slack);
 
 /* ------------------------------------------------------------------------
  * Device-side SRBD linearisation: the producer of the QP data, i.e.

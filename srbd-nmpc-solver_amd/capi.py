@@ -55,6 +55,20 @@ class Solution(C.Structure):
     _fields_ = [(n, _dp) for n in SOL_FIELDS]
 
 
+# soft boxes (srbd_qp_soft_f64 / srbd_qp_slack_f64; the header's field order)
+SOFT_FIELDS = ("soft_u", "soft_x", "Zl_u", "Zu_u", "zl_u", "zu_u", "Zl_x", "Zu_x", "zl_x", "zu_x",
+               "lls_u", "lus_u", "lls_x", "lus_x")
+SLACK_FIELDS = ("sl_u", "su_u", "sl_x", "su_x")
+
+
+class Soft(C.Structure):
+    _fields_ = [(n, _dp) for n in SOFT_FIELDS]
+
+
+class Slack(C.Structure):
+    _fields_ = [(n, _dp) for n in SLACK_FIELDS]
+
+
 # srbd_qp_solve_host_cb_f64's callback: void (*)(void* ctx)
 FACTORS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
@@ -115,6 +129,15 @@ def lib():
         L.srbd_qp_solve_host_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
                                              C.POINTER(Data), C.POINTER(Solution)]
         L.srbd_qp_solve_host_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_solve_soft_f64"):  # soft boxes (older builds: A/B runs)
+            L.srbd_qp_solve_soft_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings), C.POINTER(Data),
+                                                 C.POINTER(Soft), C.POINTER(Solution), C.POINTER(Slack),
+                                                 C.c_void_p]
+            L.srbd_qp_solve_soft_f64.restype = C.c_int
+            L.srbd_qp_solve_soft_host_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
+                                                      C.POINTER(Data), C.POINTER(Soft), C.POINTER(Solution),
+                                                      C.POINTER(Slack)]
+            L.srbd_qp_solve_soft_host_f64.restype = C.c_int
         if hasattr(L, "srbd_qp_solve_host_cb_f64"):  # ABI 12
             L.srbd_qp_solve_host_cb_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings), C.POINTER(Data),
                                                     C.POINTER(Solution), FACTORS_CB, C.c_void_p]
@@ -268,6 +291,25 @@ class Handle:
                 C.c_void_p(stream or None)), f.__name__)
         _order_after(o)
 
+    def solve_soft_device(self, batch: int, settings: Settings, data: Data, soft: Soft, sol: Solution,
+                          slack: Optional[Slack] = None, stream: int = 0, order: bool = True) -> None:
+        """srbd_qp_solve_soft_f64: solve_device with soft boxes (fp64, the batched kernels);
+        `slack` (optional) receives the slacks."""
+        o = _order_before(self, stream, order)
+        check(lib().srbd_qp_solve_soft_f64(self._h, int(batch), C.byref(settings), C.byref(data),
+                                           C.byref(soft), C.byref(sol),
+                                           C.byref(slack) if slack is not None else None,
+                                           C.c_void_p(stream or None)), "srbd_qp_solve_soft_f64")
+        _order_after(o)
+
+    def solve_soft_host(self, batch: int, settings: Settings, data: Data, soft: Soft, sol: Solution,
+                        slack: Optional[Slack] = None) -> None:
+        """srbd_qp_solve_soft_host_f64: host buffers, waits."""
+        check(lib().srbd_qp_solve_soft_host_f64(self._h, int(batch), C.byref(settings), C.byref(data),
+                                                C.byref(soft), C.byref(sol),
+                                                C.byref(slack) if slack is not None else None),
+              "srbd_qp_solve_soft_host_f64")
+
     def host_staging(self, batch: int, settings: Settings, data, sol) -> None:
         """srbd_qp_host_staging_f64: the non-NULL fields of data / sol (markers) become
         pointers into the handle's pinned staging buffer (in place)."""
@@ -405,7 +447,10 @@ def solve(qp, x0, settings: Optional[Dict] = None, device: str = "cuda:0", ricca
 
     stats=True also returns "stat" [batch][iter_max+2][18], the per-iteration
     statistics rows (alpha_aff, mu_aff, sigma, alpha_prim, alpha_dual, mu,
-    res_stat, res_eq, res_ineq, res_comp, obj, 0...)."""
+    res_stat, res_eq, res_ineq, res_comp, obj, 0...).
+
+    A batch with soft boxes (qp.has_soft) goes through srbd_qp_solve_soft_f64 (fp64) and
+    also returns the slacks "sl_u", "su_u" [batch][N][nu] and "sl_x", "su_x" [batch][N+1][nx]."""
     import torch
     if not torch.cuda.is_available():
         raise SrbdQpError("no GPU available: libsrbd_qp has no CPU fallback")
@@ -415,7 +460,17 @@ def solve(qp, x0, settings: Optional[Dict] = None, device: str = "cuda:0", ricca
     s = settings_struct(settings)
     dt, st, data, sol = device_buffers(qp, x0, device, riccati, x_init, u_init,
                                        stat_rows=(s.iter_max + 2) if stats else 0, dtype=dtype)
-    h.solve_device(qp.batch, s, data, sol)
+    if getattr(qp, "has_soft", False):
+        if np.dtype(dtype) != np.float64:
+            raise SrbdQpError("soft boxes are solved in fp64 only")
+        sk = {"sl_u": torch.zeros_like(st["u"]), "su_u": torch.zeros_like(st["u"]),
+              "sl_x": torch.zeros_like(st["pi"]), "su_x": torch.zeros_like(st["pi"])}
+        soft = Soft(**{k: _tensor_ptr(dt.get(k)) or None for k in SOFT_FIELDS})
+        slack = Slack(**{k: _tensor_ptr(v) for k, v in sk.items()})
+        h.solve_soft_device(qp.batch, s, data, soft, sol, slack)
+        st = dict(st, **sk)
+    else:
+        h.solve_device(qp.batch, s, data, sol)
     h.synchronize()
     out = {k: v.cpu().numpy() for k, v in st.items()}
     if riccati:

@@ -439,6 +439,236 @@ __device__ __forceinline__ void aff_sums(const Side& s, const Bar& b, const BarS
   }
 }
 
+// ---- soft boxes (SOFT kernels only; HPIPM's Zl / Zu / zl / zu / lls / lus) ----
+// A soft bound on v has a slack s >= sb on each active side, penalised by 1/2 Z s^2 + z s:
+//   t = w + s - bound (w = v - lb below, ub - v above),  t_s = s - sb,
+//   r_s = Z s + z - lam - lam_s                 (stationarity in s),
+//   dlam = -g - Gamma (dw + ds),  dlam_s = -g_s - Gamma_s ds   (Gamma = lam / t, g as gamma_of).
+// The slack's row Z ds - dlam - dlam_s + r_s = 0 is solved lane-locally,
+//   ds = -(r_s + g + g_s + Gamma dw) / Zt,  Zt = Z + Gamma + Gamma_s,
+// which leaves the variable's own row with
+//   Gamma_eff = Gamma (Z + Gamma_s) / Zt,  g_eff = g - Gamma (r_s + g + g_s) / Zt
+// in place of Gamma, g: the Riccati recursion sees a diagonal barrier Hessian as before.
+struct SoftIn {   // the variable's soft data: on = 1 if soft, penalties, slack bounds
+  real on, Zl, Zu, zl, zu, bl, bu;
+};
+struct SoftSt {   // slacks, and the slack bounds' t and lam
+  real sl, su, tl, tu, ll, lu;
+};
+struct SoftStep {
+  real dsl, dsu, dtl, dtu, dll, dlu;
+};
+__device__ __forceinline__ SoftSt load_soft(const real* p, int i) {
+  p += kSoftSt;
+  return SoftSt{p[i], p[12 + i], p[24 + i], p[36 + i], p[48 + i], p[60 + i]};
+}
+__device__ __forceinline__ void store_soft(real* p, int i, const SoftSt& s) {
+  p += kSoftSt;
+  p[i] = s.sl; p[12 + i] = s.su; p[24 + i] = s.tl; p[36 + i] = s.tu; p[48 + i] = s.ll; p[60 + i] = s.lu;
+}
+__device__ __forceinline__ SoftStep load_sstep(const real* p, int i) {
+  p += kSoftDlt;
+  return SoftStep{p[i], p[12 + i], p[24 + i], p[36 + i], p[48 + i], p[60 + i]};
+}
+__device__ __forceinline__ void store_sstep(real* p, int i, const SoftStep& d) {
+  p += kSoftDlt;
+  p[i] = d.dsl; p[12 + i] = d.dsu; p[24 + i] = d.dtl; p[36 + i] = d.dtu; p[48 + i] = d.dll; p[60 + i] = d.dlu;
+}
+// The soft arrays of one QP (dense per variable like the bounds; every load at a valid
+// address, masked after: see Ctx::side_at)
+struct SoftView {
+  const SoftArgsT<real>& s;
+  int N, nx, nu;
+  size_t q;
+  __device__ real* st(int k, int which) const {
+    return s.sws + q * s.sws_qp + (size_t)k * kSoftStage + which * kSoftFam;
+  }
+  __device__ static SoftIn in_at(const real* soft, const real* Zl, const real* Zu, const real* zl,
+                                 const real* zu, const real* bl, const real* bu, size_t o, bool ok) {
+    const real m = soft[o], a = Zl[o], b = Zu[o], c = zl[o], d = zu[o];
+    const real e = (bl ? bl : soft)[o], f = (bu ? bu : soft)[o];
+    const bool on = ok && m != real(0.0);
+    const real z = real(0.0);
+    return SoftIn{on ? real(1.0) : z, on ? a : z, on ? b : z, on ? c : z, on ? d : z,
+                  on && bl ? e : z, on && bu ? f : z};
+  }
+  __device__ SoftIn in_u(int k, int i) const {
+    if (!s.soft_u) return SoftIn{0, 0, 0, 0, 0, 0, 0};
+    const bool ok = i < nu && k < N;
+    const size_t o = (q * N + (k < N ? k : N - 1)) * nu + (ok ? i : 0);
+    return in_at(s.soft_u, s.Zl_u, s.Zu_u, s.zl_u, s.zu_u, s.lls_u, s.lus_u, o, ok);
+  }
+  __device__ SoftIn in_x(int k, int i) const {
+    if (!s.soft_x) return SoftIn{0, 0, 0, 0, 0, 0, 0};
+    const bool ok = i < nx && k > 0;  // stage-0 x bounds dropped
+    const size_t o = (q * (N + 1) + k) * nx + (ok ? i : 0);
+    return in_at(s.soft_x, s.Zl_x, s.Zu_x, s.zl_x, s.zu_x, s.lls_x, s.lus_x, o, ok);
+  }
+};
+// One active side of a soft variable in side-local terms (w, lam, t: the bound's pair; s, ts,
+// ls: the slack and its bound's pair; ext / exs: the corrector's predictor products).
+struct SoftOne {
+  real Gl, rd, rm, rds, rms, rsum, Zt, Geff, geff;
+};
+__device__ __forceinline__ SoftOne soft_one(real w, real lam, real t, real s, real ts, real ls, real Z,
+                                            real z, real sb, real ext, real exs, real smu) {
+  SoftOne o;
+  o.rd = w + s - t;
+  o.rm = lam * t + ext - smu;
+  o.Gl = lam / t;
+  const real gl = (o.rm + lam * o.rd) / t;
+  o.rds = s - sb - ts;
+  o.rms = ls * ts + exs - smu;
+  const real Gs = ls / ts;
+  const real gs = (o.rms + ls * o.rds) / ts;
+  o.rsum = Z * s + z - lam - ls + gl + gs;
+  o.Zt = Z + o.Gl + Gs;
+  o.Geff = o.Gl * (Z + Gs) / o.Zt;
+  o.geff = gl - o.Gl * o.rsum / o.Zt;
+  return o;
+}
+// gamma_of for a variable that may be soft
+__device__ __forceinline__ void gamma_soft(const Side& s, const Bar& b, const SoftIn& si, const SoftSt& ss,
+                                           real v, real ext_l, real ext_u, real exs_l, real exs_u, real smu,
+                                           real& G, real& g) {
+  if (si.on == real(0.0)) {
+    gamma_of(s, b, v, ext_l, ext_u, smu, G, g);
+    return;
+  }
+  G = real(0.0);
+  g = real(0.0);
+  if (s.ml != real(0.0)) {
+    const SoftOne o = soft_one(v - s.lb, b.ll, b.tl, ss.sl, ss.tl, ss.ll, si.Zl, si.zl, si.bl, ext_l, exs_l, smu);
+    G += o.Geff;
+    g += o.geff;
+  }
+  if (s.mu != real(0.0)) {
+    const SoftOne o = soft_one(s.ub - v, b.lu, b.tu, ss.su, ss.tu, ss.lu, si.Zu, si.zu, si.bu, ext_u, exs_u, smu);
+    G += o.Geff;
+    g -= o.geff;
+  }
+}
+// bar_step for a variable that may be soft: ds from dv, then dt / dlam of both pairs
+__device__ __forceinline__ void soft_step(const Side& s, const Bar& b, const SoftIn& si, const SoftSt& ss,
+                                          real v, real dv, real ext_l, real ext_u, real exs_l, real exs_u,
+                                          real smu, BarStep& d, SoftStep& e) {
+  e = SoftStep{0, 0, 0, 0, 0, 0};
+  if (si.on == real(0.0)) {
+    d = bar_step(s, b, v, dv, ext_l, ext_u, smu);
+    return;
+  }
+  d = BarStep{0, 0, 0, 0};
+  if (s.ml != real(0.0)) {
+    const SoftOne o = soft_one(v - s.lb, b.ll, b.tl, ss.sl, ss.tl, ss.ll, si.Zl, si.zl, si.bl, ext_l, exs_l, smu);
+    e.dsl = -(o.rsum + o.Gl * dv) / o.Zt;
+    d.dtl = o.rd + dv + e.dsl;
+    d.dll = -(o.rm + b.ll * d.dtl) / b.tl;
+    e.dtl = o.rds + e.dsl;
+    e.dll = -(o.rms + ss.ll * e.dtl) / ss.tl;
+  }
+  if (s.mu != real(0.0)) {
+    const SoftOne o = soft_one(s.ub - v, b.lu, b.tu, ss.su, ss.tu, ss.lu, si.Zu, si.zu, si.bu, ext_u, exs_u, smu);
+    e.dsu = -(o.rsum - o.Gl * dv) / o.Zt;
+    d.dtu = o.rd - dv + e.dsu;
+    d.dlu = -(o.rm + b.lu * d.dtu) / b.tu;
+    e.dtu = o.rds + e.dsu;
+    e.dlu = -(o.rms + ss.lu * e.dtu) / ss.tu;
+  }
+}
+// the slack bounds' pairs in the step ratios and the predictor sums
+__device__ __forceinline__ void ratio_soft(const Side& s, const SoftIn& si, const SoftSt& ss, const SoftStep& e,
+                                           real& ap, real& ad) {
+  if (si.on == real(0.0)) return;
+  if (s.ml != real(0.0)) {
+    if (e.dtl < real(0.0)) ap = fmin(ap, -ss.tl / e.dtl);
+    if (e.dll < real(0.0)) ad = fmin(ad, -ss.ll / e.dll);
+  }
+  if (s.mu != real(0.0)) {
+    if (e.dtu < real(0.0)) ap = fmin(ap, -ss.tu / e.dtu);
+    if (e.dlu < real(0.0)) ad = fmin(ad, -ss.lu / e.dlu);
+  }
+}
+__device__ __forceinline__ void aff_soft(const Side& s, const SoftIn& si, const SoftSt& ss, const SoftStep& e,
+                                         real& s1, real& s2) {
+  if (si.on == real(0.0)) return;
+  if (s.ml != real(0.0)) {
+    s1 += ss.ll * e.dtl + ss.tl * e.dll;
+    s2 += e.dll * e.dtl;
+  }
+  if (s.mu != real(0.0)) {
+    s1 += ss.lu * e.dtu + ss.tu * e.dlu;
+    s2 += e.dlu * e.dtu;
+  }
+}
+__device__ __forceinline__ bool huge_soft(const SoftStep& e) {
+  return huge(e.dsl) || huge(e.dsu) || huge(e.dtl) || huge(e.dtu) || huge(e.dll) || huge(e.dlu);
+}
+// RB's box terms of one variable that may be soft: the multipliers in its gradient residual
+// rg, and the norms of res_d (md), res_m (mm, musum), the slacks' stationarity r_s (mg) and
+// the slack penalty (obj)
+__device__ __forceinline__ void rb_soft_terms(const Side& s, const Bar& b, const SoftIn& si, const SoftSt& ss,
+                                              real v, real& rg, real& mg, real& md, real& mm, real& musum,
+                                              real& obj) {
+  const bool on = si.on != real(0.0);
+  if (s.ml != real(0.0)) {
+    rg -= b.ll;
+    const real rd = v + (on ? ss.sl : real(0.0)) - s.lb - b.tl, rm = b.ll * b.tl;
+    md = fmax(md, nabs(rd));
+    mm = fmax(mm, nabs(rm));
+    musum += rm;
+    if (on) {
+      const real rms = ss.ll * ss.tl;
+      md = fmax(md, nabs(ss.sl - si.bl - ss.tl));
+      mm = fmax(mm, nabs(rms));
+      musum += rms;
+      mg = fmax(mg, nabs(si.Zl * ss.sl + si.zl - b.ll - ss.ll));
+      obj += ss.sl * (real(0.5) * si.Zl * ss.sl + si.zl);
+    }
+  }
+  if (s.mu != real(0.0)) {
+    rg += b.lu;
+    const real rd = s.ub - v + (on ? ss.su : real(0.0)) - b.tu, rm = b.lu * b.tu;
+    md = fmax(md, nabs(rd));
+    mm = fmax(mm, nabs(rm));
+    musum += rm;
+    if (on) {
+      const real rms = ss.lu * ss.tu;
+      md = fmax(md, nabs(ss.su - si.bu - ss.tu));
+      mm = fmax(mm, nabs(rms));
+      musum += rms;
+      mg = fmax(mg, nabs(si.Zu * ss.su + si.zu - b.lu - ss.lu));
+      obj += ss.su * (real(0.5) * si.Zu * ss.su + si.zu);
+    }
+  }
+}
+// Cold start of a soft variable (the init of the same problem with its slacks written as
+// inputs boxed below by sb and the bound as a general row): v stays where it is, s = max(0,
+// sb + thr0), t_s = s - sb, t = max(w + s, thr0), lam = mu0 / t for both pairs.  Returns
+// the number of slack-bound pairs (one per active side).
+__device__ __forceinline__ real soft_init(const Side& s, const SoftIn& si, real v, real mu0, Bar& b, SoftSt& ss) {
+  ss = SoftSt{real(0.0), real(0.0), real(1.0), real(1.0), real(0.0), real(0.0)};
+  if (si.on == real(0.0)) return real(0.0);
+  b = Bar{real(0.0), real(0.0), real(1.0), real(1.0)};
+  real n = real(0.0);
+  if (s.ml != real(0.0)) {
+    ss.sl = fmax(real(0.0), si.bl + kThr0);
+    ss.tl = ss.sl - si.bl;
+    ss.ll = mu0 / ss.tl;
+    b.tl = fmax(v - s.lb + ss.sl, kThr0);
+    b.ll = mu0 / b.tl;
+    n += real(1.0);
+  }
+  if (s.mu != real(0.0)) {
+    ss.su = fmax(real(0.0), si.bu + kThr0);
+    ss.tu = ss.su - si.bu;
+    ss.lu = mu0 / ss.tu;
+    b.tu = fmax(s.ub - v + ss.su, kThr0);
+    b.lu = mu0 / b.tu;
+    n += real(1.0);
+  }
+  return n;
+}
+
 // gather an element-owned value (lane i < 12 holds v_i) into VL's registers
 __device__ __forceinline__ void gather12(real v, real (&out)[12]) {
   sfor<0, 12>([&](auto i) {
@@ -474,8 +704,16 @@ __device__ __forceinline__ int group_qp(const ProblemArgsT<real>& a) {
 // 540 B/lane into the Cholesky path too).
 template <int LQ>
 constexpr bool kLqFactor = LQ >= 2;
-template <bool FULL, int GEN, int PH, bool SQRT = false, int LQ = 0>
-__device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
+// SOFT: soft boxes (fp64, GEN == 0, LQ == 0; ipm_soft.hip).  The launch arguments then carry
+// the soft arrays behind the ProblemArgsT; every other kernel's arguments are unchanged.
+struct SoftProblemArgs : ProblemArgsT<real> {
+  SoftArgsT<real> soft;
+};
+template <bool SOFT>
+using IpmArgs = std::conditional_t<SOFT, SoftProblemArgs, ProblemArgsT<real>>;
+template <bool FULL, int GEN, int PH, bool SQRT = false, int LQ = 0, bool SOFT = false>
+__device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
+  static_assert(!SOFT || (FULL && GEN == 0 && LQ == 0 && sizeof(real) == 8), "soft boxes: fp64 box kernels");
   // the refinement check runs stage-parallel: group g on QP slot g / (N + 1), stage
   // g % (N + 1) (its rows are independent across stages); every other phase: one QP per group
   int kst = 0;
@@ -698,7 +936,9 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
       real v = (a.warm_start && uel) ? c.u()[(size_t)k * nu + li] : real(0.0);
       const Side s = c.side_u(k, lane);
       Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
-      if (s.ml != real(0.0) || s.mu != real(0.0)) {
+      [[maybe_unused]] SoftIn si{0, 0, 0, 0, 0, 0, 0};  // (a soft variable is not projected)
+      if constexpr (SOFT) si = SoftView{a.soft, N, nx, nu, c.oq()}.in_u(k, lane);
+      if (si.on == real(0.0) && (s.ml != real(0.0) || s.mu != real(0.0))) {
         real tl = v - s.lb, tu = s.ub - v;
         if (s.ml != real(0.0) && s.mu != real(0.0)) {
           if (tl < kThr0) {
@@ -730,6 +970,15 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
         bb.lu = s.mu != real(0.0) ? a.mu0 / tu : real(0.0);
       }
       ncl += s.ml + s.mu;
+      if constexpr (SOFT) {
+        SoftSt ss;
+        ncl += soft_init(s, si, v, a.mu0, bb, ss);
+        if (lane < kMaxDim) {
+          real* sp = SoftView{a.soft, N, nx, nu, c.oq()}.st(k, 0);
+          store_soft(sp, lane, ss);
+          store_sstep(sp, lane, SoftStep{0, 0, 0, 0, 0, 0});
+        }
+      }
       if (lane < kMaxDim) store_bar(stk, 0, lane, bb);
       if (uel) c.u()[(size_t)k * nu + lane] = v;
       ui = uel ? v : real(0.0);
@@ -744,7 +993,9 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
       }
       const Side s = c.side_x(k, lane);
       Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
-      if (s.ml != real(0.0) || s.mu != real(0.0)) {
+      [[maybe_unused]] SoftIn si{0, 0, 0, 0, 0, 0, 0};
+      if constexpr (SOFT) si = SoftView{a.soft, N, nx, nu, c.oq()}.in_x(k, lane);
+      if (si.on == real(0.0) && (s.ml != real(0.0) || s.mu != real(0.0))) {
         real tl = v - s.lb, tu = s.ub - v;
         if (s.ml != real(0.0) && s.mu != real(0.0)) {
           if (tl < kThr0) {
@@ -776,6 +1027,19 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
         bb.lu = s.mu != real(0.0) ? a.mu0 / tu : real(0.0);
       }
       ncl += s.ml + s.mu;
+      if constexpr (SOFT) {
+        SoftSt ss;
+        ncl += soft_init(s, si, v, a.mu0, bb, ss);
+        if (lane < kMaxDim) {
+          const SoftView sv{a.soft, N, nx, nu, c.oq()};
+          store_soft(sv.st(k, 1), lane, ss);
+          store_sstep(sv.st(k, 1), lane, SoftStep{0, 0, 0, 0, 0, 0});
+          if (k == N) {  // (no u_N: its rows hold the defaults)
+            store_soft(sv.st(N, 0), lane, SoftSt{0, 0, 1, 1, 0, 0});
+            store_sstep(sv.st(N, 0), lane, SoftStep{0, 0, 0, 0, 0, 0});
+          }
+        }
+      }
       if (lane < kMaxDim) store_bar(stk, 1, lane, bb);
       if (xel) {
         c.x()[(size_t)k * nx + lane] = v;
@@ -923,6 +1187,30 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
       }
     }
   }
+  if constexpr (SOFT) {
+    // the slacks (0 where the variable is not soft or the side is masked)
+    const SoftView sv{a.soft, N, nx, nu, c.oq()};
+    for (int k = 0; k <= N; ++k) {
+      if (k < N && uel) {
+        const Side s = c.side_u(k, lane);
+        const SoftIn si = sv.in_u(k, lane);
+        const SoftSt ss = load_soft(sv.st(k, 0), lane);
+        const bool on = si.on != real(0.0);
+        const size_t o = ((size_t)qp * N + k) * nu + lane;
+        if (a.soft.sl_u) a.soft.sl_u[o] = on && s.ml != real(0.0) ? ss.sl : real(0.0);
+        if (a.soft.su_u) a.soft.su_u[o] = on && s.mu != real(0.0) ? ss.su : real(0.0);
+      }
+      if (xel) {
+        const Side s = c.side_x(k, lane);
+        const SoftIn si = sv.in_x(k, lane);
+        const SoftSt ss = load_soft(sv.st(k, 1), lane);
+        const bool on = si.on != real(0.0);
+        const size_t o = ((size_t)qp * (N + 1) + k) * nx + lane;
+        if (a.soft.sl_x) a.soft.sl_x[o] = on && s.ml != real(0.0) ? ss.sl : real(0.0);
+        if (a.soft.su_x) a.soft.su_x[o] = on && s.mu != real(0.0) ? ss.su : real(0.0);
+      }
+    }
+  }
   if (lane == 0) {
     if (a.status) a.status[qp] = status;
     if (a.iter) a.iter[qp] = nc > real(0.0) ? iter : 0;
@@ -1018,6 +1306,18 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
       Bar bu = c.bar(stk, 0, li), bx = c.bar(stk, 1, li);
       const BarStep du = c.bstep(stk, 0, li), dx = c.bstep(stk, 1, li);
       const Side su = c.side_u(k, lane), sx = c.side_x(k, lane);
+      [[maybe_unused]] SoftIn qu, qx;      // soft data, slack state and step of u_k / x_k
+      [[maybe_unused]] SoftSt ssu, ssx;
+      [[maybe_unused]] SoftStep esu, esx;
+      if constexpr (SOFT) {
+        const SoftView sv{a.soft, N, nx, nu, c.oq()};
+        qu = sv.in_u(k, lane);
+        qx = sv.in_x(k, lane);
+        ssu = load_soft(sv.st(k, 0), li);
+        ssx = load_soft(sv.st(k, 1), li);
+        esu = load_sstep(sv.st(k, 0), li);
+        esx = load_sstep(sv.st(k, 1), li);
+      }
       const real qk = c.el(c.q() + (size_t)k * nx, nx, li);
       const real rk = k < N ? c.el(c.r() + (size_t)k * nu, nu, li) : real(0.0);
       if (k == N) c.col(c.Q() + (size_t)N * c.nxx(), nx, col, xel, P);  // P_N = Q_N + ...
@@ -1051,6 +1351,21 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
         bx.lu = step(bx.lu, alpha_d, dx.dlu);
         c.put_bar(stk, 0, lane, bu);
         c.put_bar(stk, 1, lane, bx);
+        if constexpr (SOFT) {
+          auto upd = [&](SoftSt& s, const SoftStep& e) {
+            s.sl = step(s.sl, alpha_p, e.dsl);
+            s.su = step(s.su, alpha_p, e.dsu);
+            s.tl = step(s.tl, alpha_p, e.dtl);
+            s.tu = step(s.tu, alpha_p, e.dtu);
+            s.ll = step(s.ll, alpha_d, e.dll);
+            s.lu = step(s.lu, alpha_d, e.dlu);
+          };
+          upd(ssu, esu);
+          upd(ssx, esx);
+          const SoftView sv{a.soft, N, nx, nu, c.oq()};
+          store_soft(sv.st(k, 0), lane, ssu);
+          store_soft(sv.st(k, 1), lane, ssx);
+        }
       }
       // ---- residual terms without the stage blocks (element-owned) ----
       real rgx = qk - pik, rgu = rk;
@@ -1147,6 +1462,16 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
         }
       }
       // box terms
+      real Gu = real(0.0), gu = real(0.0), Gx = real(0.0), gx = real(0.0);
+      if constexpr (SOFT) {
+        rb_soft_terms(su, bu, qu, ssu, uk, rgu, mg, md, mm, musum, objl);
+        rb_soft_terms(sx, bx, qx, ssx, xk, rgx, mg, md, mm, musum, objl);
+        if (lane < kMaxDim) {
+          const real z = real(0.0);
+          gamma_soft(su, bu, qu, ssu, uk, z, z, z, z, z, Gu, gu);
+          gamma_soft(sx, bx, qx, ssx, xk, z, z, z, z, z, Gx, gx);
+        }
+      } else {
       if (su.ml != real(0.0)) {
         rgu -= bu.ll;
         const real rd = uk - su.lb - bu.tl, rm = bu.ll * bu.tl;
@@ -1176,10 +1501,10 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
         musum += rm;
       }
       // predictor Gamma / gamma of the bounds and general rows
-      real Gu = real(0.0), gu = real(0.0), Gx = real(0.0), gx = real(0.0);
       if (lane < kMaxDim) {
         gamma_of(su, bu, uk, real(0.0), real(0.0), real(0.0), Gu, gu);
         gamma_of(sx, bx, xk, real(0.0), real(0.0), real(0.0), Gx, gx);
+      }
       }
       if constexpr (GEN == 1) {
         if (lane < kMaxDim) {
@@ -1787,7 +2112,14 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
           real G = real(0.0), g = real(0.0);
           if (lane < kMaxDim) {
             const BarStep dx = c.bstep(stN, 1, lane);
+            if constexpr (SOFT) {
+              const SoftView sv{a.soft, N, nx, nu, c.oq()};
+              const SoftStep ex = load_sstep(sv.st(N, 1), lane);
+              gamma_soft(sx, c.bar(stN, 1, lane), sv.in_x(N, lane), load_soft(sv.st(N, 1), lane), xv,
+                         dx.dll * dx.dtl, dx.dlu * dx.dtu, ex.dll * ex.dtl, ex.dlu * ex.dtu, sigma_mu, G, g);
+            } else {
             gamma_of(sx, c.bar(stN, 1, lane), xv, dx.dll * dx.dtl, dx.dlu * dx.dtu, sigma_mu, G, g);
+            }
           }
           pnext = lane < kMaxDim && xel ? stN[kStRes + 12 + lane] + g : real(0.0);
           if constexpr (GEN == 2) {
@@ -1822,6 +2154,16 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
           const real uv = uel && c.has_bars(0) ? u_ld : real(0.0);
           const real xv = xel && c.has_bars(1) ? x_ld : real(0.0);
           real Gu = real(0.0), gu = real(0.0), Gx = real(0.0), gx = real(0.0);
+          if constexpr (SOFT) {
+            if (lane < kMaxDim) {
+              const SoftView sv{a.soft, N, nx, nu, c.oq()};
+              const SoftStep eu = load_sstep(sv.st(k, 0), lane), ex = load_sstep(sv.st(k, 1), lane);
+              gamma_soft(su, bu, sv.in_u(k, lane), load_soft(sv.st(k, 0), lane), uv, du.dll * du.dtl,
+                         du.dlu * du.dtu, eu.dll * eu.dtl, eu.dlu * eu.dtu, sigma_mu, Gu, gu);
+              gamma_soft(sx, bx, sv.in_x(k, lane), load_soft(sv.st(k, 1), lane), xv, dx.dll * dx.dtl,
+                         dx.dlu * dx.dtu, ex.dll * ex.dtl, ex.dlu * ex.dtu, sigma_mu, Gx, gx);
+            }
+          } else
           if (lane < kMaxDim) {
             gamma_of(su, bu, uv, du.dll * du.dtl, du.dlu * du.dtu, sigma_mu, Gu, gu);
             gamma_of(sx, bx, xv, dx.dll * dx.dtl, dx.dlu * dx.dtu, sigma_mu, Gx, gx);
@@ -1990,8 +2332,38 @@ __device__ __forceinline__ void ipm_phase(const ProblemArgsT<real>& a) {
             exu = px.dlu * px.dtu;
             smu = sigma_mu;
           }
-          const BarStep nu_ = bar_step(su, bu, uv, du, eul, euu, smu);
-          const BarStep nx_ = bar_step(sx, bx, xv, dxk, exl, exu, smu);
+          BarStep nu_, nx_;
+          if constexpr (SOFT) {
+            const SoftView sv{a.soft, N, nx, nu, c.oq()};
+            real* const pu = sv.st(k, 0);
+            real* const px = sv.st(k, 1);
+            const SoftIn qu = sv.in_u(k, lane), qx = sv.in_x(k, lane);
+            const SoftSt ssu = load_soft(pu, lane), ssx = load_soft(px, lane);
+            real sul = real(0.0), suu = real(0.0), sxl = real(0.0), sxu = real(0.0);
+            if (corr) {
+              const SoftStep pe = load_sstep(pu, lane), qe = load_sstep(px, lane);
+              sul = pe.dll * pe.dtl;
+              suu = pe.dlu * pe.dtu;
+              sxl = qe.dll * qe.dtl;
+              sxu = qe.dlu * qe.dtu;
+            }
+            SoftStep eu_, ex_;
+            soft_step(su, bu, qu, ssu, uv, du, eul, euu, sul, suu, smu, nu_, eu_);
+            soft_step(sx, bx, qx, ssx, xv, dxk, exl, exu, sxl, sxu, smu, nx_, ex_);
+            ratio_soft(su, qu, ssu, eu_, ap, ad);
+            ratio_soft(sx, qx, ssx, ex_, ap, ad);
+            if (!corr) {
+              aff_soft(su, qu, ssu, eu_, s1, s2);
+              aff_soft(sx, qx, ssx, ex_, s1, s2);
+            }
+            store_sstep(pu, lane, eu_);
+            store_sstep(px, lane, ex_);
+            if (final_step) bad |= huge_soft(eu_) || huge_soft(ex_) || huge(nx_.dtl) || huge(nx_.dtu) ||
+                                   huge(nx_.dll) || huge(nx_.dlu);
+          } else {
+            nu_ = bar_step(su, bu, uv, du, eul, euu, smu);
+            nx_ = bar_step(sx, bx, xv, dxk, exl, exu, smu);
+          }
           ratio(su, bu, nu_, ap, ad);
           ratio(sx, bx, nx_, ap, ad);
           if (!corr) {
@@ -2102,8 +2474,8 @@ __device__ __forceinline__ bool solve_done(const ProblemArgsT<real>& a) {
   return a.ctl && __atomic_load_n(a.ctl + kCtlDone, __ATOMIC_RELAXED) != 0;
 }
 
-template <bool FULL, int GEN, int PH, bool SQRT = false, int LQ = 0>
-__global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_kernel(ProblemArgsT<real> a) {
+template <bool FULL, int GEN, int PH, bool SQRT = false, int LQ = 0, bool SOFT = false>
+__global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_kernel(IpmArgs<SOFT> a) {
   if constexpr (PH == kPhInit) {  // this solve's live-QP counters and control words start at 0
     if (a.ctl)
       for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kCtlInts; i += gridDim.x * blockDim.x)
@@ -2111,7 +2483,7 @@ __global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_
   }
   if constexpr (PH != kPhInit && PH != kPhOut)
     if (solve_done(a)) return;
-  ipm_phase<FULL, GEN, PH, SQRT, LQ>(a);
+  ipm_phase<FULL, GEN, PH, SQRT, LQ, SOFT>(a);
   if constexpr (PH == kPhRB && LQ != 3) report_running(a);  // (3: counted by the 1 launch)
 }
 
@@ -2120,12 +2492,12 @@ __global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_
 // their records are still in L2 / the Infinity Cache, and the launch count halves.
 // The second phase re-reads the per-QP state the first one wrote (same wave:
 // visible after the workgroup-scope fence).
-template <bool FULL, int GEN, int PH1, int PH2, bool SQRT = false, int LQ = 0>
-__global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase2_kernel(ProblemArgsT<real> a) {
+template <bool FULL, int GEN, int PH1, int PH2, bool SQRT = false, int LQ = 0, bool SOFT = false>
+__global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase2_kernel(IpmArgs<SOFT> a) {
   if (solve_done(a)) return;
-  ipm_phase<FULL, GEN, PH1, SQRT, LQ>(a);
+  ipm_phase<FULL, GEN, PH1, SQRT, LQ, SOFT>(a);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  ipm_phase<FULL, GEN, PH2, SQRT, LQ>(a);
+  ipm_phase<FULL, GEN, PH2, SQRT, LQ, SOFT>(a);
   if constexpr (PH1 == kPhRB && LQ != 3)  // (lq_fact 1: the LQ launch's QPs are counted, as
     if (!a.lq_redo) report_running(a);   // running, by the Cholesky launch before it)
 }
@@ -2168,8 +2540,8 @@ __global__ void __launch_bounds__(256) compact_running_kernel(const real* __rest
 #endif
 constexpr bool kIpmSplit = SRBD_IPM_SPLIT != 0;
 
-template <bool FULL, int GEN, bool SQRT, int LQ>
-static hipError_t launch_phases(const ProblemArgsT<real>& a, hipStream_t stream) {
+template <bool FULL, int GEN, bool SQRT, int LQ, bool SOFT = false>
+static hipError_t launch_phases(const IpmArgs<SOFT>& a, hipStream_t stream) {
   const int threads = 256;
   const long long lanes = (long long)a.batch * kGroup;
   const dim3 full_grid((unsigned)((lanes + threads - 1) / threads)), block(threads);
@@ -2183,7 +2555,7 @@ static hipError_t launch_phases(const ProblemArgsT<real>& a, hipStream_t stream)
   // instruction, so a finished solve's remaining launches cost their dispatch only.
   const bool ctl = a.ctl && a.iter_max < a.ctl_cap;
 
-  ProblemArgsT<real> b = a;
+  IpmArgs<SOFT> b = a;
   if (!ctl) b.ctl = nullptr;
   b.launch_it = 0;
   // Active-QP compaction (compact_decide_kernel): once the workgroups with a live QP are at
@@ -2195,24 +2567,24 @@ static hipError_t launch_phases(const ProblemArgsT<real>& a, hipStream_t stream)
   const bool compact = ctl && a.qp_buf && full_grid.x >= 64;
   // (init covers every QP and clears the control words: no list, whatever they held before)
   b.qp_list = nullptr;
-  hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhInit>), grid, block, 0, stream, b);
+  hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhInit, false, 0, SOFT>), grid, block, 0, stream, b);
   b.qp_list = compact ? a.qp_buf : nullptr;
   // (SQRT changes RB and how B2, F1, F2 and the outputs apply the record's P)
   for (int it = 0;; ++it) {
     b.launch_it = it;
     if (it >= a.iter_max) {
       if (!a.skip_last_rb) {
-        hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, LQ>), grid, block, 0, stream, b);
+        hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
         if constexpr (LQ == 1)  // (lq_fact 1: the switched QPs' RB by LQ)
           hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, 3>), grid, block, 0, stream, b);
       }
       break;
     }
     if (kIpmSplit) {  // diagnostic schedule: one launch per sweep
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, LQ>), grid, block, 0, stream, b);
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhF1, SQRT, LQ>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhF1, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
     } else {
-      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhRB, kPhF1, SQRT, LQ>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhRB, kPhF1, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
     }
     if constexpr (LQ == 1) {
       // HPIPM lq_fact 1: RB -> F1 by LQ of the QPs switched in an earlier iteration, then the
@@ -2222,7 +2594,7 @@ static hipError_t launch_phases(const ProblemArgsT<real>& a, hipStream_t stream)
       hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhIRP, SQRT>), dim3(grid.x * (unsigned)(a.N + 1)), block,
                          0, stream, b);
       hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhLqChk, SQRT>), grid, block, 0, stream, b);
-      ProblemArgsT<real> r = b;
+      IpmArgs<SOFT> r = b;
       r.lq_redo = 1;
       hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhRB, kPhF1, SQRT, 3>), grid, block, 0, stream, r);
     }
@@ -2232,14 +2604,15 @@ static hipError_t launch_phases(const ProblemArgsT<real>& a, hipStream_t stream)
                          a.ws, a.ws_qp, a.batch, a.qp_buf, a.ctl);
     }
     if (a.pred_corr && kIpmSplit) {
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhB2, SQRT>), grid, block, 0, stream, b);
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhF2, SQRT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhB2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhF2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
     } else if (a.pred_corr) {
-      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhB2, kPhF2, SQRT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhB2, kPhF2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
     }
     // HPIPM's iterative refinement of the corrector step (Balance / Robust): at
     // most itref_corr_max corrections, each after a check of the step's linear residual; a
     // QP whose check passed returns at the top of the later ones
+    if constexpr (!SOFT)  // (the refinement does not carry the slack rows)
     if (a.pred_corr)
       for (int r = 0; r < a.itref_corr_max; ++r) {
         hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhIR, SQRT>), dim3(grid.x * (unsigned)(a.N + 1)),
@@ -2248,10 +2621,23 @@ static hipError_t launch_phases(const ProblemArgsT<real>& a, hipStream_t stream)
       }
   }
   b.qp_list = nullptr;  // outputs for every QP
-  hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhOut, SQRT>), full_grid, block, 0, stream, b);
+  hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhOut, SQRT, 0, SOFT>), full_grid, block, 0, stream, b);
   return hipGetLastError();
 }
 
+#ifdef SRBD_IPM_SOFT_TU
+// the soft-box instantiations only (ipm_soft.hip): fp64 boxes, both Riccati forms
+hipError_t launch_soft(const ProblemArgsT<real>& a, const SoftArgsT<real>& s, hipStream_t stream) {
+  if (a.batch <= 0) return hipSuccess;
+  if (a.nx != 12 || a.nu != 12 || a.ng != 0 || a.itref_corr_max != 0 || a.lq_fact != 0 || a.warm_start > 1)
+    return hipErrorInvalidValue;
+  SoftProblemArgs b;
+  static_cast<ProblemArgsT<real>&>(b) = a;
+  b.soft = s;
+  if (a.ric_alg) return launch_phases<true, 0, true, 0, true>(b, stream);
+  return launch_phases<true, 0, false, 0, true>(b, stream);
+}
+#else
 // HPIPM's lq_fact (the C-ABI derives it from the mode, with ric_alg != 0 only)
 template <bool FULL, int GEN>
 static hipError_t launch_alg(const ProblemArgsT<real>& a, hipStream_t stream) {
@@ -2271,6 +2657,7 @@ hipError_t launch(const ProblemArgsT<real>& a, hipStream_t stream) {
   if (a.ng > 0) return launch_alg<true, 1>(a, stream);
   return launch_alg<true, 0>(a, stream);
 }
+#endif
 
 }  // namespace SRBD_NS
 }  // namespace srbd

@@ -131,6 +131,29 @@ constexpr int kGenChunk = 112;
 constexpr int kGenVec = 36;
 
 size_t ws_doubles_ipm(int N, int ng);  // elements per QP (either precision)
+
+// Soft box constraints (srbd_qp_solve_soft_f64; ipm_soft.hip): the slack data, outputs and
+// state of a solve, next to its ProblemArgsT (which keeps its layout).  Dense per variable
+// like the box masks: [batch][N][nu] (u) and [batch][N+1][nx] (x).  A NULL soft_u / soft_x
+// means no soft variable in that family (its other pointers are then not read); NULL lls /
+// lus mean 0; NULL outputs are not written.
+template <typename T>
+struct SoftArgsT {
+  const T *soft_u, *Zl_u, *Zu_u, *zl_u, *zu_u, *lls_u, *lus_u;
+  const T *soft_x, *Zl_x, *Zu_x, *zl_x, *zu_x, *lls_x, *lus_x;
+  T *sl_u, *su_u, *sl_x, *su_x;  // slack outputs
+  T* sws;                        // soft workspace, sws_qp elements per QP
+  size_t sws_qp;
+};
+// Soft workspace per stage (element-owned 12-wide rows like kStLam / kStDlt, u then x): per
+// family the slacks s_l, s_u, the slack bounds' t_sl, t_su, lam_sl, lam_su, then their steps
+constexpr int kSoftSt = 0;     // 6 x 12: s_l s_u t_sl t_su lam_sl lam_su
+constexpr int kSoftDlt = 72;   // 6 x 12: their steps
+constexpr int kSoftFam = 144;  // per family
+constexpr int kSoftStage = 2 * kSoftFam;
+size_t ws_doubles_soft(int N);  // soft workspace elements per QP
+// The batched fp64 IPM with soft boxes (12 x 12 stages, no general rows, no refinement)
+hipError_t launch_ipm_soft(const ProblemArgsT<double>& a, const SoftArgsT<double>& s, hipStream_t stream);
 // The one-launch latency IPM (ipm_latency.hip): fp64, both Riccati forms, HPIPM's refinement, up
 // to max_batch QPs (one workgroup each).  ipm_latency_ok says whether `a` runs there;
 // launch_ipm_box_batched always takes the batched kernels.
@@ -194,6 +217,14 @@ template <typename T>
 hipError_t pad_problem(const ProblemArgsT<T>& a, T* buf, ProblemArgsT<T>& o, hipStream_t s);
 template <typename T>
 hipError_t unpad_solution(const ProblemArgsT<T>& a, const ProblemArgsT<T>& o, hipStream_t s);
+// The soft arrays of an embedded problem (a: the caller's dims): pad_soft fills `buf`
+// (pad_soft_elems elements) and returns the 12-wide arrays and slack outputs in `o` (padded
+// variables: soft mask 0; sws is taken over); unpad_slack copies the slacks back into s's.
+size_t pad_soft_elems(int batch, int N);
+hipError_t pad_soft(const ProblemArgsT<double>& a, const SoftArgsT<double>& s, double* buf,
+                    SoftArgsT<double>& o, hipStream_t strm);
+hipError_t unpad_slack(const ProblemArgsT<double>& a, const SoftArgsT<double>& s,
+                       const SoftArgsT<double>& o, hipStream_t strm);
 
 }  // namespace srbd
 #include "../../include/srbd_qp.h"

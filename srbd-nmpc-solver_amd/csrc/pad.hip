@@ -174,6 +174,69 @@ hipError_t unpad_solution(const ProblemArgsT<T>& a, const ProblemArgsT<T>& o, hi
   return e;
 }
 
+// Soft boxes of an embedded problem: the 14 soft arrays and the 4 slack outputs, 12 wide.
+// Padded variables get soft mask 0 (and zero penalties / slack bounds, never read).
+namespace {
+struct SoftPadLayout {
+  size_t in_u[7], in_x[7], out_u[2], out_x[2], total;
+  SoftPadLayout(size_t batch, size_t N) {
+    size_t o = 0;
+    auto take = [&](size_t n) {
+      const size_t at = o;
+      o += (n + 31) / 32 * 32;
+      return at;
+    };
+    for (size_t& v : in_u) v = take(batch * N * 12);
+    for (size_t& v : in_x) v = take(batch * (N + 1) * 12);
+    for (size_t& v : out_u) v = take(batch * N * 12);
+    for (size_t& v : out_x) v = take(batch * (N + 1) * 12);
+    total = o;
+  }
+};
+}  // namespace
+
+size_t pad_soft_elems(int batch, int N) { return SoftPadLayout(batch, N).total; }
+
+hipError_t pad_soft(const ProblemArgsT<double>& a, const SoftArgsT<double>& s, double* buf,
+                    SoftArgsT<double>& o, hipStream_t strm) {
+  const SoftPadLayout L(a.batch, a.N);
+  const long long Bq = a.batch, N = a.N;
+  o = s;
+  hipError_t e = hipSuccess;
+  auto P = [&](const double* src, size_t off, long long nblk, int sr, const double*& field) {
+    if (e != hipSuccess) return;
+    field = nullptr;
+    if (!src) return;  // (NULL slack bounds stay NULL = 0)
+    e = pad<double>(src, buf + off, nblk, sr, 1, 12, 1, 0.0, 0.0, 0.0, strm);
+    field = buf + off;
+  };
+  if (s.soft_u) {
+    const double* const src[7] = {s.soft_u, s.Zl_u, s.Zu_u, s.zl_u, s.zu_u, s.lls_u, s.lus_u};
+    const double** const dst[7] = {&o.soft_u, &o.Zl_u, &o.Zu_u, &o.zl_u, &o.zu_u, &o.lls_u, &o.lus_u};
+    for (int i = 0; i < 7; ++i) P(src[i], L.in_u[i], Bq * N, a.nu, *dst[i]);
+  }
+  if (s.soft_x) {
+    const double* const src[7] = {s.soft_x, s.Zl_x, s.Zu_x, s.zl_x, s.zu_x, s.lls_x, s.lus_x};
+    const double** const dst[7] = {&o.soft_x, &o.Zl_x, &o.Zu_x, &o.zl_x, &o.zu_x, &o.lls_x, &o.lus_x};
+    for (int i = 0; i < 7; ++i) P(src[i], L.in_x[i], Bq * (N + 1), a.nx, *dst[i]);
+  }
+  o.sl_u = s.sl_u ? buf + L.out_u[0] : nullptr;
+  o.su_u = s.su_u ? buf + L.out_u[1] : nullptr;
+  o.sl_x = s.sl_x ? buf + L.out_x[0] : nullptr;
+  o.su_x = s.su_x ? buf + L.out_x[1] : nullptr;
+  return e;
+}
+
+hipError_t unpad_slack(const ProblemArgsT<double>& a, const SoftArgsT<double>& s,
+                       const SoftArgsT<double>& o, hipStream_t strm) {
+  const long long Bq = a.batch, N = a.N;
+  hipError_t e = unpad<double>(o.sl_u, s.sl_u, Bq * N, a.nu, 1, 12, 1, strm);
+  if (e == hipSuccess) e = unpad<double>(o.su_u, s.su_u, Bq * N, a.nu, 1, 12, 1, strm);
+  if (e == hipSuccess) e = unpad<double>(o.sl_x, s.sl_x, Bq * (N + 1), a.nx, 1, 12, 1, strm);
+  if (e == hipSuccess) e = unpad<double>(o.su_x, s.su_x, Bq * (N + 1), a.nx, 1, 12, 1, strm);
+  return e;
+}
+
 template hipError_t pad_problem<double>(const ProblemArgsT<double>&, double*, ProblemArgsT<double>&,
                                         hipStream_t);
 template hipError_t pad_problem<float>(const ProblemArgsT<float>&, float*, ProblemArgsT<float>&,

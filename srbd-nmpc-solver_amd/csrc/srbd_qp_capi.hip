@@ -60,6 +60,12 @@ struct srbd_qp_handle_s {
   // nx < 12 or nu < 12: the 12 x 12 embedding (pad.hip), allocated on first use
   void* pad = nullptr;
   size_t pad_bytes = 0;
+  // srbd_qp_solve_soft_f64: the slack state (capacity QPs) and, for embedded problems, the
+  // 12-wide soft arrays and slack outputs, allocated on first use
+  double* soft_ws = nullptr;
+  size_t soft_ws_bytes = 0;
+  void* soft_pad = nullptr;
+  size_t soft_pad_bytes = 0;
   // srbd_qp_srbd_nmpc_f64: QP data, solution and loop state, allocated on first use
   void* nmpc = nullptr;
   size_t nmpc_bytes = 0;
@@ -357,6 +363,8 @@ void srbd_qp_destroy(srbd_qp_handle h) {
   if (h->stage) hipFree(h->stage);
   if (h->pinned) hipHostFree(h->pinned);
   if (h->pad) hipFree(h->pad);
+  if (h->soft_ws) hipFree(h->soft_ws);
+  if (h->soft_pad) hipFree(h->soft_pad);
   if (h->nmpc) hipFree(h->nmpc);
   if (h->nmpc_active_host) hipHostFree(h->nmpc_active_host);
   if (h->resc_idx) hipFree(h->resc_idx);
@@ -383,6 +391,7 @@ size_t srbd_qp_workspace_bytes(srbd_qp_handle h) { return h ? h->ws_bytes : 0; }
 size_t srbd_qp_memory_bytes(srbd_qp_handle h) {
   if (!h) return 0;
   return h->ws_bytes + h->stage_bytes + h->pinned_bytes + h->pad_bytes + h->nmpc_bytes +
+         h->soft_ws_bytes + h->soft_pad_bytes +
          (h->ctl ? sizeof(int) * srbd::kCtlInts : 0) +
          (h->qp_buf ? sizeof(int) * ((size_t)h->capacity + 1) : 0) +
          h->resc_bytes + h->resc2_bytes + h->mixed_bytes + h->lqsw_bytes +
@@ -1270,8 +1279,213 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
   return SRBD_QP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Soft box constraints (srbd_qp_solve_soft_f64): always the batched fp64 kernels
+// ---------------------------------------------------------------------------
+static int solve_soft_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
+                           const srbd_qp_data_f64* d, const srbd_qp_soft_f64* sf,
+                           const srbd_qp_solution_f64* s, const srbd_qp_slack_f64* sl, void* stream) {
+  int rc = validate_call(h, batch, st, d, s);
+  if (rc) return rc;
+  if (!sf) return fail(SRBD_QP_EINVAL, "soft is NULL");
+  const srbd_qp_dims& dm = h->dims;
+  if (dm.ng > 0)
+    return fail(SRBD_QP_EDIM, "soft boxes: general rows (ng > 0) are not supported, got ng = " +
+                                  std::to_string(dm.ng));
+  if (st->mode == SRBD_QP_MODE_BALANCE || st->mode == SRBD_QP_MODE_ROBUST)
+    return fail(SRBD_QP_ESETTINGS, "soft boxes: mode Balance / Robust is not supported (the iterative "
+                                   "refinement does not carry the slack rows); use Speed or SpeedAbs");
+  if (st->f32_iters != 0 || st->f64_rescue != 0)
+    return fail(SRBD_QP_ESETTINGS, "soft boxes: f32_iters and f64_rescue must be 0 (fp64 only)");
+  if (st->ric_alg && st->lq_fact > 0)
+    return fail(SRBD_QP_ESETTINGS, "soft boxes: lq_fact must be 0 or -1 (Cholesky factorizations only)");
+  if (st->warm_start != 0 && st->warm_start != 1)
+    return fail(SRBD_QP_ESETTINGS, "soft boxes: warm_start must be 0 or 1");
+  if (sf->soft_u && !dm.has_box_u) return fail(SRBD_QP_EINVAL, "soft_u needs a handle with has_box_u");
+  if (sf->soft_x && !dm.has_box_x) return fail(SRBD_QP_EINVAL, "soft_x needs a handle with has_box_x");
+  if (!constrained(dm)) return fail(SRBD_QP_EINVAL, "soft boxes need a handle with has_box_u or has_box_x");
+  if (sf->soft_u && (!sf->Zl_u || !sf->Zu_u || !sf->zl_u || !sf->zu_u))
+    return fail(SRBD_QP_EINVAL, "soft_u needs Zl_u, Zu_u, zl_u and zu_u");
+  if (sf->soft_x && (!sf->Zl_x || !sf->Zu_x || !sf->zl_x || !sf->zu_x))
+    return fail(SRBD_QP_EINVAL, "soft_x needs Zl_x, Zu_x, zl_x and zu_x");
+  if (batch == 0) return SRBD_QP_OK;
+  hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  int prev = 0;
+  hipGetDevice(&prev);
+  hipSetDevice(h->device);
+  const bool padded = dm.nx != 12 || dm.nu != 12;
+  // first-use buffers: allocated into locals, committed to the handle only when all succeeded
+  {
+    const size_t ws_need = srbd::ws_doubles_soft(dm.N) * sizeof(double) * (size_t)h->capacity;
+    const size_t sp_need = padded ? srbd::pad_soft_elems(h->capacity, dm.N) * sizeof(double) : 0;
+    const size_t pd_need = padded ? srbd::pad_elems(h->capacity, dm.N, 0) * sizeof(double) : 0;
+    void *nws = nullptr, *nsp = nullptr, *npd = nullptr;
+    hipError_t ea = hipSuccess;
+    if (ws_need > h->soft_ws_bytes) ea = hipMalloc(&nws, ws_need);
+    if (ea == hipSuccess && sp_need > h->soft_pad_bytes) ea = hipMalloc(&nsp, sp_need);
+    if (ea == hipSuccess && pd_need > h->pad_bytes) ea = hipMalloc(&npd, pd_need);
+    if (ea != hipSuccess) {
+      if (nws) hipFree(nws);
+      if (nsp) hipFree(nsp);
+      if (npd) hipFree(npd);
+      hipSetDevice(prev);
+      return fail(SRBD_QP_ENOMEM, std::string("soft-box buffers: ") + hipGetErrorString(ea));
+    }
+    if (nws) {
+      if (h->soft_ws) hipFree(h->soft_ws);
+      h->soft_ws = static_cast<double*>(nws);
+      h->soft_ws_bytes = ws_need;
+    }
+    if (nsp) {
+      if (h->soft_pad) hipFree(h->soft_pad);
+      h->soft_pad = nsp;
+      h->soft_pad_bytes = sp_need;
+    }
+    if (npd) {
+      if (h->pad) hipFree(h->pad);
+      h->pad = npd;
+      h->pad_bytes = pd_need;
+    }
+  }
+  srbd::ProblemArgsT<double> a = build_args<double>(h, batch, st, d, s, s->status, nullptr, 0);
+  a.itref_corr_max = 0;
+  a.lq_fact = 0;
+  srbd::SoftArgsT<double> soft;
+  std::memset(&soft, 0, sizeof soft);
+  soft.soft_u = sf->soft_u; soft.Zl_u = sf->Zl_u; soft.Zu_u = sf->Zu_u; soft.zl_u = sf->zl_u;
+  soft.zu_u = sf->zu_u; soft.lls_u = sf->lls_u; soft.lus_u = sf->lus_u;
+  soft.soft_x = sf->soft_x; soft.Zl_x = sf->Zl_x; soft.Zu_x = sf->Zu_x; soft.zl_x = sf->zl_x;
+  soft.zu_x = sf->zu_x; soft.lls_x = sf->lls_x; soft.lus_x = sf->lus_x;
+  if (sl) {
+    soft.sl_u = sl->sl_u; soft.su_u = sl->su_u; soft.sl_x = sl->sl_x; soft.su_x = sl->su_x;
+  }
+  soft.sws = h->soft_ws;
+  soft.sws_qp = srbd::ws_doubles_soft(dm.N);
+  hipError_t e = hipSuccess;
+  if (s->stat)
+    e = hipMemsetAsync(s->stat, 0,
+                       sizeof(double) * srbd::kStatCols * (size_t)(st->iter_max + 2) * (size_t)batch, strm);
+  srbd::ProblemArgsT<double> run = a;
+  srbd::SoftArgsT<double> srun = soft;
+  if (e == hipSuccess && padded) {
+    e = srbd::pad_problem<double>(a, reinterpret_cast<double*>(h->pad), run, strm);
+    if (e == hipSuccess) e = srbd::pad_soft(a, soft, reinterpret_cast<double*>(h->soft_pad), srun, strm);
+  }
+  if (e == hipSuccess) e = srbd::launch_ipm_soft(run, srun, strm);
+  if (e == hipSuccess && padded) {
+    e = srbd::unpad_solution<double>(a, run, strm);
+    if (e == hipSuccess) e = srbd::unpad_slack(a, soft, srun, strm);
+  }
+  hipSetDevice(prev);
+  if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+  return SRBD_QP_OK;
+}
+
+// The host-buffer call: one device buffer for the call's arrays, freed before it returns.
+static int solve_soft_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
+                                const srbd_qp_data_f64* d, const srbd_qp_soft_f64* sf,
+                                const srbd_qp_solution_f64* s, const srbd_qp_slack_f64* sl) {
+  int rc = validate_call(h, batch, st, d, s);
+  if (rc) return rc;
+  if (!sf) return fail(SRBD_QP_EINVAL, "soft is NULL");
+  if (s->P || s->p || s->K || s->k || s->stat)
+    return fail(SRBD_QP_EINVAL, "srbd_qp_solve_soft_host_f64 does not return P, p, K, k or stat");
+  if (batch == 0) return SRBD_QP_OK;
+  const srbd_qp_dims& dm = h->dims;
+  const size_t B = (size_t)batch, N = (size_t)dm.N, nx = (size_t)dm.nx, nu = (size_t)dm.nu, ng = (size_t)dm.ng;
+  struct Item {
+    const void* src;  // host input (NULL: output only)
+    void* dst;        // host output (NULL: input only)
+    size_t bytes;
+    void** dev;       // the device struct's field
+  };
+  std::vector<Item> items;
+  srbd_qp_data_f64 dd = *d;
+  srbd_qp_soft_f64 ds = *sf;
+  srbd_qp_solution_f64 dsol = *s;
+  srbd_qp_slack_f64 dsl{nullptr, nullptr, nullptr, nullptr};
+  if (sl) dsl = *sl;
+  auto in = [&](const double*& f, size_t elems) {
+    if (f) items.push_back(Item{f, nullptr, elems * sizeof(double), (void**)&f});
+  };
+  auto out = [&](double*& f, size_t elems, bool also_in = false) {
+    if (f) items.push_back(Item{also_in ? f : nullptr, f, elems * sizeof(double), (void**)&f});
+  };
+  in(dd.A, B * N * nx * nx); in(dd.B, B * N * nx * nu); in(dd.b, B * N * nx);
+  in(dd.Q, B * (N + 1) * nx * nx); in(dd.S, B * N * nu * nx); in(dd.R, B * N * nu * nu);
+  in(dd.q, B * (N + 1) * nx); in(dd.r, B * N * nu); in(dd.x0, B * nx);
+  in(dd.lbu, B * N * nu); in(dd.ubu, B * N * nu); in(dd.lbu_mask, B * N * nu); in(dd.ubu_mask, B * N * nu);
+  in(dd.lbx, B * (N + 1) * nx); in(dd.ubx, B * (N + 1) * nx);
+  in(dd.lbx_mask, B * (N + 1) * nx); in(dd.ubx_mask, B * (N + 1) * nx);
+  in(dd.C, B * (N + 1) * ng * nx); in(dd.D, B * N * ng * nu);
+  in(dd.lg, B * (N + 1) * ng); in(dd.ug, B * (N + 1) * ng);
+  in(dd.lg_mask, B * (N + 1) * ng); in(dd.ug_mask, B * (N + 1) * ng);
+  in(ds.soft_u, B * N * nu); in(ds.Zl_u, B * N * nu); in(ds.Zu_u, B * N * nu); in(ds.zl_u, B * N * nu);
+  in(ds.zu_u, B * N * nu); in(ds.lls_u, B * N * nu); in(ds.lus_u, B * N * nu);
+  in(ds.soft_x, B * (N + 1) * nx); in(ds.Zl_x, B * (N + 1) * nx); in(ds.Zu_x, B * (N + 1) * nx);
+  in(ds.zl_x, B * (N + 1) * nx); in(ds.zu_x, B * (N + 1) * nx); in(ds.lls_x, B * (N + 1) * nx);
+  in(ds.lus_x, B * (N + 1) * nx);
+  out(dsol.x, B * (N + 1) * nx, st->warm_start != 0); out(dsol.u, B * N * nu, st->warm_start != 0);
+  out(dsol.pi, B * (N + 1) * nx); out(dsol.res, B * 4); out(dsol.obj, B);
+  out(dsl.sl_u, B * N * nu); out(dsl.su_u, B * N * nu);
+  out(dsl.sl_x, B * (N + 1) * nx); out(dsl.su_x, B * (N + 1) * nx);
+  int *h_status = s->status, *h_iter = s->iter;
+  size_t total = 0;
+  auto round = [](size_t b) { return (b + 255) / 256 * 256; };
+  for (const Item& it : items) total += round(it.bytes);
+  const size_t int_off = total;
+  total += 2 * round(B * sizeof(int));
+  int prev = 0;
+  hipGetDevice(&prev);
+  hipSetDevice(h->device);
+  char* buf = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), total);
+  if (e != hipSuccess) {
+    hipSetDevice(prev);
+    return fail(SRBD_QP_ENOMEM, std::string("soft host solve buffer: ") + hipGetErrorString(e));
+  }
+  size_t off = 0;
+  for (Item& it : items) {
+    *it.dev = buf + off;
+    if (e == hipSuccess && it.src)
+      e = hipMemcpyAsync(buf + off, it.src, it.bytes, hipMemcpyHostToDevice, h->stream);
+    off += round(it.bytes);
+  }
+  dsol.status = h_status ? reinterpret_cast<int*>(buf + int_off) : nullptr;
+  dsol.iter = h_iter ? reinterpret_cast<int*>(buf + int_off + round(B * sizeof(int))) : nullptr;
+  hipSetDevice(prev);
+  if (e == hipSuccess) rc = solve_soft_impl(h, batch, st, &dd, &ds, &dsol, sl ? &dsl : nullptr, h->stream);
+  hipSetDevice(h->device);
+  if (e == hipSuccess && rc == SRBD_QP_OK) {
+    for (Item& it : items)
+      if (e == hipSuccess && it.dst)
+        e = hipMemcpyAsync(it.dst, *it.dev, it.bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && h_status)
+      e = hipMemcpyAsync(h_status, dsol.status, B * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && h_iter)
+      e = hipMemcpyAsync(h_iter, dsol.iter, B * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = es;
+  hipFree(buf);
+  hipSetDevice(prev);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("soft host solve: ") + hipGetErrorString(e));
+  return SRBD_QP_OK;
+}
+
 extern "C" {
 
+int srbd_qp_solve_soft_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
+                           const srbd_qp_data_f64* d, const srbd_qp_soft_f64* sf,
+                           const srbd_qp_solution_f64* s, const srbd_qp_slack_f64* sl, void* stream) {
+  return solve_soft_impl(h, batch, st, d, sf, s, sl, stream);
+}
+int srbd_qp_solve_soft_host_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
+                                const srbd_qp_data_f64* d, const srbd_qp_soft_f64* sf,
+                                const srbd_qp_solution_f64* s, const srbd_qp_slack_f64* sl) {
+  return solve_soft_host_impl(h, batch, st, d, sf, s, sl);
+}
 int srbd_qp_solve_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
                       const srbd_qp_data_f64* d, const srbd_qp_solution_f64* s, void* stream) {
   return solve_impl<double>(h, batch, st, d, s, stream);

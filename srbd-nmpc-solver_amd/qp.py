@@ -54,6 +54,10 @@ def dense_box_from_index(n: int, idx, lb, ub, lb_mask=None, ub_mask=None):
     return lbd, ubd, lmd, umd
 
 
+SOFT_FIELDS = ("soft_u", "Zl_u", "Zu_u", "zl_u", "zu_u", "lls_u", "lus_u",
+               "soft_x", "Zl_x", "Zu_x", "zl_x", "zu_x", "lls_x", "lus_x")
+
+
 @dataclass
 class OcpQpBatch:
     """A batch of OCP-QPs with uniform dimensions (N, nx, nu, ng)."""
@@ -84,6 +88,23 @@ class OcpQpBatch:
     ug: Optional[np.ndarray] = None
     lg_mask: Optional[np.ndarray] = None
     ug_mask: Optional[np.ndarray] = None
+    # soft boxes (srbd_qp_soft_f64): dense per variable like the masks.  soft_* = 1 marks the
+    # variable's box as soft; Z* / z* are the slack penalties 1/2 Z s^2 + z s per side
+    # (default 0), lls_* / lus_* the slacks' lower bounds (default 0)
+    soft_u: Optional[np.ndarray] = None  # (batch, N, nu)
+    soft_x: Optional[np.ndarray] = None  # (batch, N+1, nx); stage 0 ignored
+    Zl_u: Optional[np.ndarray] = None
+    Zu_u: Optional[np.ndarray] = None
+    zl_u: Optional[np.ndarray] = None
+    zu_u: Optional[np.ndarray] = None
+    Zl_x: Optional[np.ndarray] = None
+    Zu_x: Optional[np.ndarray] = None
+    zl_x: Optional[np.ndarray] = None
+    zu_x: Optional[np.ndarray] = None
+    lls_u: Optional[np.ndarray] = None
+    lus_u: Optional[np.ndarray] = None
+    lls_x: Optional[np.ndarray] = None
+    lus_x: Optional[np.ndarray] = None
     meta: Dict = field(default_factory=dict)
 
     @property
@@ -97,6 +118,11 @@ class OcpQpBatch:
     @property
     def has_box_x(self) -> bool:
         return self.lbx is not None
+
+    @property
+    def has_soft(self) -> bool:
+        """True when a soft_u / soft_x mask is given (the solve takes srbd_qp_solve_soft_f64)."""
+        return self.soft_u is not None or self.soft_x is not None
 
     @property
     def has_general(self) -> bool:
@@ -136,6 +162,8 @@ class OcpQpBatch:
             want[name] = (bt, N + 1, ng)
         want["C"] = (bt, N + 1, ng, nx)
         want["D"] = (bt, N, ng, nu)
+        for name in SOFT_FIELDS:
+            want[name] = (bt, N, nu) if name.endswith("_u") else (bt, N + 1, nx)
         for name, shape in want.items():
             arr = getattr(self, name)
             if arr is None:
@@ -148,6 +176,15 @@ class OcpQpBatch:
             raise ValueError("lbx and ubx must be given together")
         if self.ng > 0 and (self.lg is None or self.ug is None):
             raise ValueError("ng > 0 requires lg and ug")
+        if self.soft_u is not None and self.lbu is None:
+            raise ValueError("soft_u requires lbu and ubu")
+        if self.soft_x is not None and self.lbx is None:
+            raise ValueError("soft_x requires lbx and ubx")
+        for fam in ("u", "x"):
+            if getattr(self, "soft_" + fam) is None:
+                given = [n for n in SOFT_FIELDS if n.endswith("_" + fam) and getattr(self, n) is not None]
+                if given:
+                    raise ValueError(f"{given[0]} requires soft_{fam}")
 
     def packed(self) -> Dict[str, Optional[np.ndarray]]:
         """C-ABI buffers (float64, contiguous, column-major per block)."""
@@ -163,13 +200,23 @@ class OcpQpBatch:
         if self.ng == 0:
             for name in ("C", "D", "lg", "ug", "lg_mask", "ug_mask"):
                 out[name] = None
+        for fam, like in (("u", self.r), ("x", self.q)):
+            if getattr(self, "soft_" + fam) is None:
+                continue
+            for name in SOFT_FIELDS:
+                if not name.endswith("_" + fam):
+                    continue
+                v = getattr(self, name)
+                if v is None and not name.startswith("l"):  # penalties default to 0 (lls / lus: NULL)
+                    v = np.zeros(like.shape)
+                out[name] = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
         return out
 
     def subset(self, idx) -> "OcpQpBatch":
         """A new batch holding QPs ``idx`` (index array or slice)."""
         kw = {}
         for name in ("A", "B", "b", "Q", "S", "R", "q", "r", "lbu", "ubu", "lbu_mask", "ubu_mask",
-                     "lbx", "ubx", "lbx_mask", "ubx_mask", "C", "D", "lg", "ug", "lg_mask", "ug_mask"):
+                     "lbx", "ubx", "lbx_mask", "ubx_mask", "C", "D", "lg", "ug", "lg_mask", "ug_mask") + SOFT_FIELDS:
             v = getattr(self, name)
             kw[name] = None if v is None else np.ascontiguousarray(v[idx])
         return OcpQpBatch(N=self.N, nx=self.nx, nu=self.nu, ng=self.ng, meta=dict(self.meta), **kw)
