@@ -20,7 +20,16 @@ HPIPM_BENCH := build/call_pattern_bench
 CXXFLAGS ?= -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
 HPIPM_INC := -Iinclude -I$(HPIPM_DIR)/include
 
-all: $(LIB) $(HPIPM_LIB) $(HPIPM_TEST) $(HPIPM_BENCH) oracle
+FIELDS_TEST := build/qp_fields_test
+
+all: $(LIB) $(HPIPM_LIB) $(HPIPM_TEST) $(HPIPM_BENCH) $(FIELDS_TEST) oracle
+
+# host-only checks of the C-ABI's field table (csrc/qp_fields.h), under the sanitizers (their
+# runtimes linked statically: the program then also runs where the environment preloads a library)
+$(FIELDS_TEST): $(CSRC)/test/qp_fields_test.cpp $(CSRC)/qp_fields.h include/srbd_qp.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -static-libasan -static-libubsan -o $@ $<
 
 # hpipm-cpp interface (host C++ over the C-ABI); rpath $ORIGIN finds libsrbd_qp.so
 $(OBJDIR)/hpipm/%.o: $(HPIPM_DIR)/src/%.cpp $(HPIPM_HDRS)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/srbd_qp.h"
+#include "device_guard.h"
 
 struct srbd_qp_multi_s {
   srbd_qp_dims dims{};
@@ -45,20 +46,19 @@ int srbd_qp_multi_create(const srbd_qp_dims* dims, int capacity_per_device, cons
   }
   // peer access root <-> shard (xGMI); a device with itself, or a pair without peer access,
   // still copies (the runtime stages the copy)
-  int prev = 0;
-  hipGetDevice(&prev);
+  auto enable_peer = [](int on, int peer) {
+    srbd::DeviceGuard guard(on);
+    (void)hipDeviceEnablePeerAccess(peer, 0);  // (already enabled: fine)
+  };
   for (int i = 1; i < ndev; ++i) {
     if (m->dev[i] == m->dev[0]) continue;
     int can = 0;
     if (hipDeviceCanAccessPeer(&can, m->dev[0], m->dev[i]) == hipSuccess && can) {
-      hipSetDevice(m->dev[0]);
-      (void)hipDeviceEnablePeerAccess(m->dev[i], 0);  // (already enabled: fine)
-      hipSetDevice(m->dev[i]);
-      (void)hipDeviceEnablePeerAccess(m->dev[0], 0);
+      enable_peer(m->dev[0], m->dev[i]);
+      enable_peer(m->dev[i], m->dev[0]);
     }
   }
   (void)hipGetLastError();
-  hipSetDevice(prev);
   *out = m;
   return SRBD_QP_OK;
 }
@@ -101,13 +101,11 @@ int multi_solve(srbd_qp_multi m, const int* batch, const srbd_qp_settings* setti
     }
   }
   // the gather: shard i's rows behind its solve, on its stream
-  int prev = 0;
-  hipGetDevice(&prev);
   hipError_t e = hipSuccess;
   size_t row = 0;
   for (int i = 0; i < n && e == hipSuccess; ++i) {
     const size_t b = (size_t)batch[i];
-    hipSetDevice(m->dev[i]);
+    srbd::DeviceGuard guard(m->dev[i]);
     hipStream_t s = reinterpret_cast<hipStream_t>(srbd_qp_stream(m->h[i]));
     auto copy = [&](T* dst, const T* src, size_t per_qp) {
       if (e != hipSuccess || !dst || !src || !b) return;
@@ -118,7 +116,6 @@ int multi_solve(srbd_qp_multi m, const int* batch, const srbd_qp_settings* setti
     copy(root_pi, sol[i].pi, (N + 1) * nx);
     row += b;
   }
-  hipSetDevice(prev);
   int rc = SRBD_QP_OK;
   for (int i = 0; i < n; ++i) {
     const int r = srbd_qp_synchronize(m->h[i]);

@@ -9,7 +9,9 @@
 // dispatch to the HIP kernels.  No CPU fallback exists: without a GPU every
 // solve returns SRBD_QP_EDEVICE.
 #include "../../include/srbd_qp.h"
+#include "device_guard.h"
 #include "kernels.h"
+#include "qp_fields.h"
 
 #include <hip/hip_runtime.h>
 
@@ -40,9 +42,38 @@ int fail(int code, const std::string& msg) {
 namespace srbd {
 // the thread's last-error message, for the other translation units of the ABI (multi.hip)
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
+
+// A buffer the handle allocates on first use and grows on demand (device memory, or pinned
+// host memory).  Call with the handle's device current.
+struct __attribute__((visibility("hidden"))) Buffer {
+  void* p = nullptr;
+  size_t bytes = 0;
+  bool pinned_host = false;
+
+  // at least `need` bytes; the old block is freed only once the new one is there (contents
+  // are not carried over)
+  hipError_t reserve(size_t need) {
+    if (need <= bytes) return hipSuccess;
+    void* fresh = nullptr;
+    const hipError_t e = pinned_host ? hipHostMalloc(&fresh, need) : hipMalloc(&fresh, need);
+    if (e != hipSuccess) return e;
+    release();
+    p = fresh;
+    bytes = need;
+    return hipSuccess;
+  }
+  void release() {
+    if (p) (void)(pinned_host ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    bytes = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
 }  // namespace srbd
 
 struct srbd_qp_handle_s {
+  __attribute__((visibility("hidden"))) srbd_qp_handle_s() = default;  // (no exported symbol)
   srbd_qp_dims dims{};
   int capacity = 0;
   int device = 0;
@@ -50,46 +81,41 @@ struct srbd_qp_handle_s {
   double* ws = nullptr;
   size_t ws_qp = 0;  // doubles per QP
   size_t ws_bytes = 0;
+  // The buffers allocated on first use (each_buffer lists them)
   // host-solve staging (device)
-  double* stage = nullptr;
-  size_t stage_bytes = 0;
+  srbd::Buffer stage;
   // small host solves (batch 1: the reference's call pattern): pinned mirror of the
   // staging buffer, so inputs go over in one copy and the outputs come back in one
-  void* pinned = nullptr;
-  size_t pinned_bytes = 0;
-  // nx < 12 or nu < 12: the 12 x 12 embedding (pad.hip), allocated on first use
-  void* pad = nullptr;
-  size_t pad_bytes = 0;
+  srbd::Buffer pinned{nullptr, 0, true};
+  // nx < 12 or nu < 12: the 12 x 12 embedding (pad.hip)
+  srbd::Buffer pad;
   // srbd_qp_solve_soft_f64: the slack state (capacity QPs) and, for embedded problems, the
-  // 12-wide soft arrays and slack outputs, allocated on first use
-  double* soft_ws = nullptr;
-  size_t soft_ws_bytes = 0;
-  void* soft_pad = nullptr;
-  size_t soft_pad_bytes = 0;
-  // srbd_qp_srbd_nmpc_f64: QP data, solution and loop state, allocated on first use
-  void* nmpc = nullptr;
-  size_t nmpc_bytes = 0;
+  // 12-wide soft arrays and slack outputs
+  srbd::Buffer soft_ws, soft_pad;
+  // srbd_qp_srbd_nmpc_f64: QP data, solution and loop state
+  srbd::Buffer nmpc;
+  // settings.f64_rescue: the compact fp64 batch, and that of the cold fp64 re-solve of
+  // rescued QPs the continuation left unsolved
+  srbd::Buffer resc, resc2;
+  // settings.f32_iters: fp32 copy of the data, fp32 iterate, barrier state
+  srbd::Buffer mixed;
+  // the latency IPM's lq_fact 1 switch: the compact batch for the batched kernels
+  srbd::Buffer lqsw;
+  template <typename F>
+  void each_buffer(F&& f) {
+    for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &resc, &resc2, &mixed, &lqsw})
+      f(*b);
+  }
   int* nmpc_active_host = nullptr;  // pinned
-  // settings.f64_rescue: unsolved-QP list + status (capacity ints each, then the count),
-  // and the compact fp64 batch, allocated on first use
+  // Select-index buffers (reserve_select): the unsolved-QP list + status (capacity ints each,
+  // then the count) of settings.f64_rescue / f32_iters, and the count's read-back (pinned)
   int* resc_idx = nullptr;
-  int* resc_count_host = nullptr;  // pinned
-  void* resc = nullptr;
-  size_t resc_bytes = 0;
-  // the cold fp64 re-solve of rescued QPs the continuation left unsolved (first use)
-  void* resc2 = nullptr;
-  size_t resc2_bytes = 0;
-  // settings.f32_iters: fp32 copy of the data, fp32 iterate, barrier state (first use)
-  void* mixed = nullptr;
-  size_t mixed_bytes = 0;
-  // the latency IPM's lq_fact 1 switch: its flag (device) and read-back (pinned), the list,
-  // status and count of the QPs that raised it (capacity ints each, then the count) and their
-  // compact batch for the batched kernels (first use); force_batched while those are solved
+  int* resc_count_host = nullptr;
+  // the lq switch's flag (device) and read-back (pinned), and the list, status and count of
+  // the QPs that raised it; force_batched while those are solved
   int* lat_flag = nullptr;
   int* lat_flag_host = nullptr;
   int* lqsw_idx = nullptr;
-  void* lqsw = nullptr;
-  size_t lqsw_bytes = 0;
   bool force_batched = false;
   // live-QP control of the IPM launch sequence (ProblemArgsT::ctl): device counters and
   // control words, decided on the device (the host never waits on them)
@@ -217,9 +243,8 @@ int srbd_qp_create(const srbd_qp_dims* dims, int batch_capacity, int device, srb
     return fail(SRBD_QP_EDEVICE, "no HIP device available (libsrbd_qp has no CPU fallback)");
   if (device < 0 || device >= ndev)
     return fail(SRBD_QP_EDEVICE, "device index " + std::to_string(device) + " out of range");
-  int prev = 0;
-  hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return fail(SRBD_QP_EDEVICE, "hipSetDevice failed");
+  srbd::DeviceGuard guard(device);
+  if (guard.status() != hipSuccess) return fail(SRBD_QP_EDEVICE, "hipSetDevice failed");
   auto* h = new srbd_qp_handle_s();
   h->dims = *dims;
   h->capacity = batch_capacity;
@@ -235,7 +260,6 @@ int srbd_qp_create(const srbd_qp_dims* dims, int batch_capacity, int device, srb
     if (e == hipSuccess) e = hipMemset(h->ctl, 0, sizeof(int) * srbd::kCtlInts);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->qp_buf), sizeof(int) * ((size_t)batch_capacity + 1));
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     srbd_qp_destroy(h);
     return fail(e == hipErrorOutOfMemory ? SRBD_QP_ENOMEM : SRBD_QP_EDEVICE,
@@ -348,39 +372,60 @@ static hipError_t server_launch(srbd_qp_handle h, const srbd::ProblemArgsT<doubl
   return e;
 }
 
+// a select-index list: QP list + status (capacity ints each), then the count
+static size_t select_idx_bytes(srbd_qp_handle h) { return sizeof(int) * (2 * (size_t)h->capacity + 1); }
+
+// The select-index buffers of a fallback, on the handle's device: the list *idx (resc_idx or
+// lqsw_idx), the count's read-back and, with_flag, the lq switch's flag and its read-back.
+// What is missing is allocated into locals and committed only when every allocation succeeded,
+// so no later call finds the set half there.
+static hipError_t reserve_select(srbd_qp_handle h, int** idx, bool with_flag) {
+  int *nidx = nullptr, *ncount = nullptr, *nflag = nullptr, *nflag_host = nullptr;
+  hipError_t e = hipSuccess;
+  auto dev = [&](int** p, size_t bytes) {
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), bytes);
+  };
+  auto host = [&](int** p) {
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(p), sizeof(int));
+  };
+  if (!*idx) dev(&nidx, select_idx_bytes(h));
+  if (!h->resc_count_host) host(&ncount);
+  if (with_flag && !h->lat_flag) {
+    dev(&nflag, sizeof(int));
+    host(&nflag_host);
+  }
+  if (e != hipSuccess) {
+    if (nidx) hipFree(nidx);
+    if (ncount) hipHostFree(ncount);
+    if (nflag) hipFree(nflag);
+    if (nflag_host) hipHostFree(nflag_host);
+    return e;
+  }
+  if (nidx) *idx = nidx;
+  if (ncount) h->resc_count_host = ncount;
+  if (nflag) {
+    h->lat_flag = nflag;
+    h->lat_flag_host = nflag_host;
+  }
+  return hipSuccess;
+}
+
 extern "C" {
 
 void srbd_qp_destroy(srbd_qp_handle h) {
   if (!h) return;
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   server_stop(h);
   if (h->srv_stream) hipStreamDestroy(h->srv_stream);
   if (h->srv_mb) hipHostFree(h->srv_mb);
   if (h->ws) hipFree(h->ws);
-  if (h->stage) hipFree(h->stage);
-  if (h->pinned) hipHostFree(h->pinned);
-  if (h->pad) hipFree(h->pad);
-  if (h->soft_ws) hipFree(h->soft_ws);
-  if (h->soft_pad) hipFree(h->soft_pad);
-  if (h->nmpc) hipFree(h->nmpc);
-  if (h->nmpc_active_host) hipHostFree(h->nmpc_active_host);
-  if (h->resc_idx) hipFree(h->resc_idx);
-  if (h->resc) hipFree(h->resc);
-  if (h->resc2) hipFree(h->resc2);
-  if (h->mixed) hipFree(h->mixed);
-  if (h->resc_count_host) hipHostFree(h->resc_count_host);
-  if (h->fac_flags) hipHostFree(h->fac_flags);
-  if (h->lat_flag) hipFree(h->lat_flag);
-  if (h->lat_flag_host) hipHostFree(h->lat_flag_host);
-  if (h->lqsw_idx) hipFree(h->lqsw_idx);
-  if (h->lqsw) hipFree(h->lqsw);
-  if (h->ctl) hipFree(h->ctl);
-  if (h->qp_buf) hipFree(h->qp_buf);
+  h->each_buffer([](srbd::Buffer& b) { b.release(); });
+  for (int* dev : {h->resc_idx, h->lat_flag, h->lqsw_idx, h->ctl, h->qp_buf})
+    if (dev) hipFree(dev);
+  for (int* host : {h->nmpc_active_host, h->resc_count_host, h->lat_flag_host, h->fac_flags})
+    if (host) hipHostFree(host);
   if (h->stream) hipStreamDestroy(h->stream);
-  hipSetDevice(prev);
   delete h;
 }
 
@@ -390,13 +435,11 @@ size_t srbd_qp_workspace_bytes(srbd_qp_handle h) { return h ? h->ws_bytes : 0; }
 
 size_t srbd_qp_memory_bytes(srbd_qp_handle h) {
   if (!h) return 0;
-  return h->ws_bytes + h->stage_bytes + h->pinned_bytes + h->pad_bytes + h->nmpc_bytes +
-         h->soft_ws_bytes + h->soft_pad_bytes +
-         (h->ctl ? sizeof(int) * srbd::kCtlInts : 0) +
-         (h->qp_buf ? sizeof(int) * ((size_t)h->capacity + 1) : 0) +
-         h->resc_bytes + h->resc2_bytes + h->mixed_bytes + h->lqsw_bytes +
-         (h->resc_idx ? sizeof(int) * (2 * (size_t)h->capacity + 1) : 0) +
-         (h->lqsw_idx ? sizeof(int) * (2 * (size_t)h->capacity + 1) : 0);
+  size_t total = h->ws_bytes + (h->ctl ? sizeof(int) * srbd::kCtlInts : 0) +
+                 (h->qp_buf ? sizeof(int) * ((size_t)h->capacity + 1) : 0) +
+                 (h->resc_idx ? select_idx_bytes(h) : 0) + (h->lqsw_idx ? select_idx_bytes(h) : 0);
+  h->each_buffer([&](const srbd::Buffer& b) { total += b.bytes; });
+  return total;
 }
 
 int srbd_qp_synchronize(srbd_qp_handle h) {
@@ -407,6 +450,14 @@ int srbd_qp_synchronize(srbd_qp_handle h) {
 }
 
 }  // extern "C"
+
+// The QP arrays of the ABI's structs are listed once, in qp_fields.h
+namespace fields = srbd::fields;
+static_assert(fields::kStatRowWidth == srbd::kStatCols, "qp_fields.h and kernels.h disagree on the stat row");
+namespace {
+// visitor of a (source, destination) pair of structs: the destination points where the source does
+constexpr auto copy_pointer = [](size_t, const auto& src, auto& dst) { dst = src; };
+}  // namespace
 
 template <typename DataT, typename SolT>
 static int validate_call(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const DataT* d,
@@ -438,7 +489,7 @@ static int mixed_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
 static int fallback_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
                         const srbd_qp_data_f64* d, const srbd_qp_solution_f64* sc,
                         const srbd_qp_solution_f64* s, hipStream_t strm, int min_status, int* idx,
-                        int* count, void** buf, size_t* buf_bytes, const double* warm_x = nullptr,
+                        int* count, srbd::Buffer& buf, const double* warm_x = nullptr,
                         const double* warm_u = nullptr);
 
 // The launch arguments of a solve (solve_impl; the resident server's request).
@@ -453,15 +504,9 @@ static srbd::ProblemArgsT<T> build_args(srbd_qp_handle h, int batch, const srbd_
   a.nu = h->dims.nu;
   a.ng = h->dims.ng;
   a.layout = h->dims.layout;
-  a.A = d->A; a.B = d->B; a.b = d->b; a.Q = d->Q; a.S = d->S; a.R = d->R; a.q = d->q; a.r = d->r;
-  a.x0 = d->x0;
-  a.lbu = d->lbu; a.ubu = d->ubu; a.lbu_mask = d->lbu_mask; a.ubu_mask = d->ubu_mask;
-  a.lbx = d->lbx; a.ubx = d->ubx; a.lbx_mask = d->lbx_mask; a.ubx_mask = d->ubx_mask;
-  a.C = d->C; a.D = d->D; a.lg = d->lg; a.ug = d->ug; a.lg_mask = d->lg_mask; a.ug_mask = d->ug_mask;
-  a.x = s->x; a.u = s->u; a.pi = s->pi;
-  a.P = s->P; a.p = s->p; a.K = s->K; a.k = s->k;
-  a.status = status; a.iter = s->iter; a.res = s->res; a.obj = s->obj;
-  a.stat = s->stat;
+  fields::for_each_input(h->dims, copy_pointer, *d, a);
+  fields::for_each_solution_field(h->dims, 0, copy_pointer, copy_pointer, *s, a);
+  a.status = status;  // (the caller's, or the handle's own list)
   a.ws = reinterpret_cast<T*>(h->ws);
   a.ws_qp = h->ws_qp;
   a.reg = st->reg_prim;
@@ -511,19 +556,12 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
         h->dims.nu == 12)
       return mixed_f64(h, batch, st, d, s, strm);
   }
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   // fp32 with f64_rescue: the status the fp32 pass leaves decides what is solved again
   const bool rescue = std::is_same_v<T, float> && st->f64_rescue && constrained(h->dims);
-  if (rescue && !h->resc_idx) {
-    hipError_t ea = hipMalloc(reinterpret_cast<void**>(&h->resc_idx),
-                              sizeof(int) * (2 * (size_t)h->capacity + 1));
-    if (ea == hipSuccess) ea = hipHostMalloc(reinterpret_cast<void**>(&h->resc_count_host), sizeof(int));
-    if (ea != hipSuccess) {
-      hipSetDevice(prev);
-      return fail(SRBD_QP_ENOMEM, std::string("rescue buffers: ") + hipGetErrorString(ea));
-    }
+  if (rescue) {
+    const hipError_t ea = reserve_select(h, &h->resc_idx, false);
+    if (ea != hipSuccess) return fail(SRBD_QP_ENOMEM, std::string("rescue buffers: ") + hipGetErrorString(ea));
   }
   int* status = s->status;
   if (rescue && !status) status = h->resc_idx + h->capacity;
@@ -540,15 +578,8 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
   const bool padded = a.nx != 12 || a.nu != 12;
   srbd::ProblemArgsT<T> run = a;
   if (e == hipSuccess && padded) {
-    const size_t need = srbd::pad_elems(h->capacity, a.N, a.ng) * sizeof(T);
-    if (need > h->pad_bytes) {
-      if (h->pad) hipFree(h->pad);
-      h->pad = nullptr;
-      h->pad_bytes = 0;
-      e = hipMalloc(&h->pad, need);
-      if (e == hipSuccess) h->pad_bytes = need;
-    }
-    if (e == hipSuccess) e = srbd::pad_problem<T>(a, reinterpret_cast<T*>(h->pad), run, strm);
+    e = h->pad.reserve(srbd::pad_elems(h->capacity, a.N, a.ng) * sizeof(T));
+    if (e == hipSuccess) e = srbd::pad_problem<T>(a, h->pad.as<T>(), run, strm);
   }
   if (e != hipSuccess) {
   } else if (constrained(h->dims)) {
@@ -560,14 +591,7 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
     bool lq_watch = false;
     if constexpr (std::is_same_v<T, double>) {
       if (run.ric_alg && run.lq_fact == 1 && iter_cap < 0 && !h->force_batched) {
-        if (!h->lat_flag) {
-          e = hipMalloc(reinterpret_cast<void**>(&h->lat_flag), sizeof(int));
-          if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->lat_flag_host), sizeof(int));
-          if (e == hipSuccess)
-            e = hipMalloc(reinterpret_cast<void**>(&h->lqsw_idx), sizeof(int) * (2 * (size_t)h->capacity + 1));
-          if (e == hipSuccess && !h->resc_count_host)
-            e = hipHostMalloc(reinterpret_cast<void**>(&h->resc_count_host), sizeof(int));
-        }
+        e = reserve_select(h, &h->lqsw_idx, true);
         run.lat_lq_flag = e == hipSuccess ? h->lat_flag : nullptr;
         lq_watch = e == hipSuccess && srbd::ipm_latency_ok(run, srbd::ipm_latency_max_batch());
         if (!lq_watch) {
@@ -590,10 +614,9 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
         if (e == hipSuccess && *h->lat_flag_host) {
           SolT sc = *s;
           sc.status = a.status;
-          hipSetDevice(prev);
           h->force_batched = true;
           rc = fallback_f64(h, batch, st, d, &sc, s, strm, srbd::kLatNeedsLq, h->lqsw_idx,
-                            h->lqsw_idx + 2 * (size_t)h->capacity, &h->lqsw, &h->lqsw_bytes);
+                            h->lqsw_idx + 2 * (size_t)h->capacity, h->lqsw);
           h->force_batched = false;
           return rc;
         }
@@ -601,10 +624,8 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
     }
     if constexpr (std::is_same_v<T, float>) {
       if (e == hipSuccess && rescue) {
-        hipSetDevice(prev);
         e = rescue_f32(h, batch, st, d, s, status, strm, &rc);
         if (rc) return rc;
-        hipSetDevice(h->device);
       }
     }
   } else {
@@ -624,7 +645,6 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
       }
     }
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -632,80 +652,68 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
 // ---------------------------------------------------------------------------
 // settings.f64_rescue: the QPs an fp32 pass left unsolved, solved again in fp64
 // ---------------------------------------------------------------------------
+// The compact fp64 batch of R selected QPs, shared by the rescue and the fallback: the values
+// per QP of every input (d) and real-valued output (s) the caller passed ...
+template <typename DataT, typename SolT>
+static size_t passed_elems(const srbd_qp_dims& m, size_t stat_rows, const DataT& d, const SolT& s) {
+  size_t total = 0;
+  auto add = [&](size_t n, const auto& f) { total += f ? n : 0; };
+  fields::for_each_input(m, add, d);
+  fields::for_each_output(m, stat_rows, add, s);
+  return total;
+}
+// ... and its layout from `cur` on: each input gathered by gather(src, dst, values per QP) with
+// d2 pointing at it, then the outputs' places in s2.  Returns the end.
+template <typename DataT, typename SolT, typename Gather>
+static double* compact_batch(const srbd_qp_dims& m, size_t stat_rows, size_t R, double* cur, const DataT& d,
+                             const SolT& s, srbd_qp_data_f64& d2, srbd_qp_solution_f64& s2, hipError_t& e,
+                             Gather&& gather) {
+  fields::for_each_input(m, [&](size_t n, const auto& src, auto& dst) {
+    if (!src || e != hipSuccess) return;
+    e = gather(src, cur, n);
+    dst = cur;
+    cur += n * R;
+  }, d, d2);
+  fields::for_each_output(m, stat_rows, [&](size_t n, const auto& dst, auto& src) {
+    if (!dst) return;
+    src = cur;
+    cur += n * R;
+  }, s, s2);
+  return cur;
+}
+
 static hipError_t rescue_f32(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
                              const srbd_qp_data_f32* d, const srbd_qp_solution_f32* s,
                              const int* status, hipStream_t strm, int* rc) {
   *rc = SRBD_QP_OK;
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   int* idx = h->resc_idx;
   int* count = h->resc_idx + 2 * (size_t)h->capacity;
   hipError_t e = srbd::launch_select_unsolved(status, batch, 1, idx, count, strm);
   if (e == hipSuccess) e = hipMemcpyAsync(h->resc_count_host, count, sizeof(int), hipMemcpyDeviceToHost, strm);
   if (e == hipSuccess) e = hipStreamSynchronize(strm);
   const int R = e == hipSuccess ? *h->resc_count_host : 0;
-  if (e != hipSuccess || R == 0) {
-    hipSetDevice(prev);
-    return e;
-  }
+  if (e != hipSuccess || R == 0) return e;
   const srbd_qp_dims& m = h->dims;
-  const size_t N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu, ng = (size_t)m.ng;
-  const size_t stat_e = srbd::kStatCols * (size_t)(st->iter_max + 2);
-  // (fp32 source, values per QP) of every input the caller passed, then every output
-  struct In { const float* src; size_t e; const double** dst; };
-  struct Out { float* dst; size_t e; double** src; };
+  const size_t N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu;
+  const size_t stat_rows = (size_t)(st->iter_max + 2);
   srbd_qp_data_f64 d64{};
   srbd_qp_solution_f64 s64{};
-  const In ins[] = {
-      {d->A, N * nx * nx, &d64.A}, {d->B, N * nx * nu, &d64.B}, {d->b, N * nx, &d64.b},
-      {d->Q, (N + 1) * nx * nx, &d64.Q}, {d->S, N * nu * nx, &d64.S}, {d->R, N * nu * nu, &d64.R},
-      {d->q, (N + 1) * nx, &d64.q}, {d->r, N * nu, &d64.r}, {d->x0, nx, &d64.x0},
-      {d->lbu, N * nu, &d64.lbu}, {d->ubu, N * nu, &d64.ubu}, {d->lbu_mask, N * nu, &d64.lbu_mask},
-      {d->ubu_mask, N * nu, &d64.ubu_mask}, {d->lbx, (N + 1) * nx, &d64.lbx},
-      {d->ubx, (N + 1) * nx, &d64.ubx}, {d->lbx_mask, (N + 1) * nx, &d64.lbx_mask},
-      {d->ubx_mask, (N + 1) * nx, &d64.ubx_mask}, {d->C, (N + 1) * ng * nx, &d64.C},
-      {d->D, N * ng * nu, &d64.D}, {d->lg, (N + 1) * ng, &d64.lg}, {d->ug, (N + 1) * ng, &d64.ug},
-      {d->lg_mask, (N + 1) * ng, &d64.lg_mask}, {d->ug_mask, (N + 1) * ng, &d64.ug_mask}};
-  const Out outs[] = {
-      {s->x, (N + 1) * nx, &s64.x}, {s->u, N * nu, &s64.u}, {s->pi, (N + 1) * nx, &s64.pi},
-      {s->P, (N + 1) * nx * nx, &s64.P}, {s->p, (N + 1) * nx, &s64.p}, {s->K, N * nu * nx, &s64.K},
-      {s->k, N * nu, &s64.k}, {s->res, 4, &s64.res}, {s->obj, 1, &s64.obj}, {s->stat, stat_e, &s64.stat}};
   // fp64 continuation from the fp32 iterate (x, u, pi and the barrier state: HPIPM's
   // warm_start = 2) on 12 x 12 stages; a padded problem is re-solved cold
   const bool cont = m.nx == 12 && m.nu == 12;
   const size_t warm_e = cont ? (N + 1) * (96 + (size_t)((m.ng + 11) / 12) * 48) : 0;
-  size_t per_qp = warm_e;  // doubles
-  for (const In& f : ins) per_qp += f.src ? f.e : 0;
-  for (const Out& f : outs) per_qp += f.dst ? f.e : 0;
-  const size_t need = sizeof(double) * per_qp * (size_t)R + 2 * sizeof(int) * (size_t)R + 256;
-  if (need > h->resc_bytes) {
-    if (h->resc) hipFree(h->resc);
-    h->resc = nullptr;
-    h->resc_bytes = 0;
-    e = hipMalloc(&h->resc, need);
-    if (e != hipSuccess) {
-      hipSetDevice(prev);
-      *rc = fail(SRBD_QP_ENOMEM, std::string("rescue batch: ") + hipGetErrorString(e));
-      return e;
-    }
-    h->resc_bytes = need;
+  const size_t per_qp = warm_e + passed_elems(m, stat_rows, *d, *s);  // doubles
+  e = h->resc.reserve(sizeof(double) * per_qp * (size_t)R + 2 * sizeof(int) * (size_t)R + 256);
+  if (e != hipSuccess) {
+    *rc = fail(SRBD_QP_ENOMEM, std::string("rescue batch: ") + hipGetErrorString(e));
+    return e;
   }
-  double* cur = reinterpret_cast<double*>(h->resc);
-  for (const In& f : ins) {
-    if (!f.src || e != hipSuccess) continue;
-    e = srbd::launch_gather_widen(f.src, cur, idx, R, f.e, strm);
-    *f.dst = cur;
-    cur += f.e * (size_t)R;
-  }
-  for (const Out& f : outs) {
-    if (!f.dst) continue;
-    *f.src = cur;
-    cur += f.e * (size_t)R;
-  }
-  double* warm = cur;
-  cur += warm_e * (size_t)R;
-  s64.status = reinterpret_cast<int*>(cur);
+  double* warm = compact_batch(m, stat_rows, (size_t)R, h->resc.as<double>(), *d, *s, d64, s64, e,
+                               [&](const float* src, double* dst, size_t n) {
+                                 return srbd::launch_gather_widen(src, dst, idx, R, n, strm);
+                               });
+  s64.status = reinterpret_cast<int*>(warm + warm_e * (size_t)R);
   s64.iter = s64.status + R;
   if (cont && e == hipSuccess) {
     // the iterate the fp32 pass ended on: x, u, pi (caller's buffers), barrier state (its
@@ -717,7 +725,6 @@ static hipError_t rescue_f32(srbd_qp_handle h, int batch, const srbd_qp_settings
       e = srbd::launch_gather_warm_bars(reinterpret_cast<const float*>(h->ws), h->ws_qp, m.N, m.ng, idx,
                                         R, warm, strm);
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) return e;
   srbd_qp_settings st64 = *st;
   st64.warm_start = cont ? 2 : 0;
@@ -731,15 +738,14 @@ static hipError_t rescue_f32(srbd_qp_handle h, int batch, const srbd_qp_settings
   // [capacity, 2 capacity) of resc_idx)
   if (cont) {
     *rc = fallback_f64(h, R, &st64, &d64, &s64, &s64, strm, 1, h->resc_idx + h->capacity,
-                       h->resc_idx + 2 * (size_t)h->capacity, &h->resc2, &h->resc2_bytes);
+                       h->resc_idx + 2 * (size_t)h->capacity, h->resc2);
     if (*rc) return hipSuccess;
   }
-  hipSetDevice(h->device);
-  for (const Out& f : outs)
-    if (f.dst && e == hipSuccess) e = srbd::launch_scatter_narrow(*f.src, f.dst, idx, R, f.e, strm);
+  fields::for_each_output(m, stat_rows, [&](size_t n, const auto& dst, const auto& src) {
+    if (dst && e == hipSuccess) e = srbd::launch_scatter_narrow(src, dst, idx, R, n, strm);
+  }, *s, s64);
   if (e == hipSuccess && s->status) e = srbd::launch_scatter_int(s64.status, s->status, idx, R, strm);
   if (e == hipSuccess && s->iter) e = srbd::launch_scatter_int(s64.iter, s->iter, idx, R, strm);
-  hipSetDevice(prev);
   return e;
 }
 
@@ -754,84 +760,42 @@ static hipError_t rescue_f32(srbd_qp_handle h, int batch, const srbd_qp_settings
 static int fallback_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
                         const srbd_qp_data_f64* d, const srbd_qp_solution_f64* sc,
                         const srbd_qp_solution_f64* s, hipStream_t strm, int min_status, int* idx,
-                        int* count, void** buf, size_t* buf_bytes, const double* warm_x, const double* warm_u) {
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
+                        int* count, srbd::Buffer& buf, const double* warm_x, const double* warm_u) {
+  srbd::DeviceGuard guard(h->device);
   hipError_t e = srbd::launch_select_unsolved(sc->status, batch, min_status, idx, count, strm);
   if (e == hipSuccess) e = hipMemcpyAsync(h->resc_count_host, count, sizeof(int), hipMemcpyDeviceToHost, strm);
   if (e == hipSuccess) e = hipStreamSynchronize(strm);
   const int R = e == hipSuccess ? *h->resc_count_host : 0;
-  if (e != hipSuccess || R == 0) {
-    hipSetDevice(prev);
-    return e == hipSuccess ? SRBD_QP_OK : fail(SRBD_QP_EDEVICE, std::string("fallback: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("fallback: ") + hipGetErrorString(e));
+  if (R == 0) return SRBD_QP_OK;
   const srbd_qp_dims& m = h->dims;
-  const size_t N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu, ng = (size_t)m.ng;
-  struct In { const double* src; size_t e; const double** dst; };
-  struct Out { double* dst; size_t e; double** src; };
+  const size_t N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu;
+  const size_t stat_rows = (size_t)(st->iter_max + 2);
   srbd_qp_data_f64 d2{};
   srbd_qp_solution_f64 s2{};
-  const In ins[] = {
-      {d->A, N * nx * nx, &d2.A}, {d->B, N * nx * nu, &d2.B}, {d->b, N * nx, &d2.b},
-      {d->Q, (N + 1) * nx * nx, &d2.Q}, {d->S, N * nu * nx, &d2.S}, {d->R, N * nu * nu, &d2.R},
-      {d->q, (N + 1) * nx, &d2.q}, {d->r, N * nu, &d2.r}, {d->x0, nx, &d2.x0},
-      {d->lbu, N * nu, &d2.lbu}, {d->ubu, N * nu, &d2.ubu}, {d->lbu_mask, N * nu, &d2.lbu_mask},
-      {d->ubu_mask, N * nu, &d2.ubu_mask}, {d->lbx, (N + 1) * nx, &d2.lbx},
-      {d->ubx, (N + 1) * nx, &d2.ubx}, {d->lbx_mask, (N + 1) * nx, &d2.lbx_mask},
-      {d->ubx_mask, (N + 1) * nx, &d2.ubx_mask}, {d->C, (N + 1) * ng * nx, &d2.C},
-      {d->D, N * ng * nu, &d2.D}, {d->lg, (N + 1) * ng, &d2.lg}, {d->ug, (N + 1) * ng, &d2.ug},
-      {d->lg_mask, (N + 1) * ng, &d2.lg_mask}, {d->ug_mask, (N + 1) * ng, &d2.ug_mask}};
-  const Out outs[] = {
-      {s->x, (N + 1) * nx, &s2.x}, {s->u, N * nu, &s2.u}, {s->pi, (N + 1) * nx, &s2.pi},
-      {s->P, (N + 1) * nx * nx, &s2.P}, {s->p, (N + 1) * nx, &s2.p}, {s->K, N * nu * nx, &s2.K},
-      {s->k, N * nu, &s2.k}, {s->res, 4, &s2.res}, {s->obj, 1, &s2.obj},
-      {s->stat, srbd::kStatCols * (size_t)(st->iter_max + 2), &s2.stat}};
-  size_t per_qp = 0;
-  for (const In& f : ins) per_qp += f.src ? f.e : 0;
-  for (const Out& f : outs) per_qp += f.dst ? f.e : 0;
-  const size_t need = sizeof(double) * per_qp * (size_t)R + 2 * sizeof(int) * (size_t)R + 256;
-  if (need > *buf_bytes) {
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    *buf_bytes = 0;
-    e = hipMalloc(buf, need);
-    if (e != hipSuccess) {
-      hipSetDevice(prev);
-      return fail(SRBD_QP_ENOMEM, std::string("fallback batch: ") + hipGetErrorString(e));
-    }
-    *buf_bytes = need;
-  }
-  double* cur = reinterpret_cast<double*>(*buf);
-  for (const In& f : ins) {
-    if (!f.src || e != hipSuccess) continue;
-    e = srbd::launch_gather_rows(f.src, cur, idx, R, f.e, strm);
-    *f.dst = cur;
-    cur += f.e * (size_t)R;
-  }
-  for (const Out& f : outs) {
-    if (!f.dst) continue;
-    *f.src = cur;
-    cur += f.e * (size_t)R;
-  }
-  s2.status = reinterpret_cast<int*>(cur);
+  const size_t per_qp = passed_elems(m, stat_rows, *d, *s);
+  e = buf.reserve(sizeof(double) * per_qp * (size_t)R + 2 * sizeof(int) * (size_t)R + 256);
+  if (e != hipSuccess) return fail(SRBD_QP_ENOMEM, std::string("fallback batch: ") + hipGetErrorString(e));
+  double* end = compact_batch(m, stat_rows, (size_t)R, buf.as<double>(), *d, *s, d2, s2, e,
+                              [&](const double* src, double* dst, size_t n) {
+                                return srbd::launch_gather_rows(src, dst, idx, R, n, strm);
+                              });
+  s2.status = reinterpret_cast<int*>(end);
   s2.iter = s2.status + R;
   const bool warm = warm_x && warm_u && st->warm_start;
   if (warm && e == hipSuccess) e = srbd::launch_gather_rows(warm_x, s2.x, idx, R, (N + 1) * nx, strm);
   if (warm && e == hipSuccess) e = srbd::launch_gather_rows(warm_u, s2.u, idx, R, N * nu, strm);
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("fallback: ") + hipGetErrorString(e));
   srbd_qp_settings st2 = *st;
   st2.warm_start = warm ? st->warm_start : 0;
   st2.f32_iters = 0;
   int rc = solve_impl<double>(h, R, &st2, &d2, &s2, strm);
   if (rc) return rc;
-  hipSetDevice(h->device);
-  for (const Out& f : outs)
-    if (f.dst && e == hipSuccess) e = srbd::launch_scatter_rows(*f.src, f.dst, idx, R, f.e, strm);
+  fields::for_each_output(m, stat_rows, [&](size_t n, const auto& dst, const auto& src) {
+    if (dst && e == hipSuccess) e = srbd::launch_scatter_rows(src, dst, idx, R, n, strm);
+  }, *s, s2);
   if (e == hipSuccess) e = srbd::launch_scatter_int(s2.status, sc->status, idx, R, strm);
   if (e == hipSuccess && s->iter) e = srbd::launch_scatter_int(s2.iter, s->iter, idx, R, strm);
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("fallback: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -839,43 +803,18 @@ static int fallback_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
 static int mixed_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
                      const srbd_qp_data_f64* d, const srbd_qp_solution_f64* s, hipStream_t strm) {
   const srbd_qp_dims& m = h->dims;
-  const size_t B = (size_t)batch, N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu,
-               ng = (size_t)m.ng;
-  srbd_qp_data_f32 d32{};
-  struct F { const double* src; size_t e; const float** dst; };
-  const F ins[] = {
-      {d->A, N * nx * nx, &d32.A}, {d->B, N * nx * nu, &d32.B}, {d->b, N * nx, &d32.b},
-      {d->Q, (N + 1) * nx * nx, &d32.Q}, {d->S, N * nu * nx, &d32.S}, {d->R, N * nu * nu, &d32.R},
-      {d->q, (N + 1) * nx, &d32.q}, {d->r, N * nu, &d32.r}, {d->x0, nx, &d32.x0},
-      {d->lbu, N * nu, &d32.lbu}, {d->ubu, N * nu, &d32.ubu}, {d->lbu_mask, N * nu, &d32.lbu_mask},
-      {d->ubu_mask, N * nu, &d32.ubu_mask}, {d->lbx, (N + 1) * nx, &d32.lbx},
-      {d->ubx, (N + 1) * nx, &d32.ubx}, {d->lbx_mask, (N + 1) * nx, &d32.lbx_mask},
-      {d->ubx_mask, (N + 1) * nx, &d32.ubx_mask}, {d->C, (N + 1) * ng * nx, &d32.C},
-      {d->D, N * ng * nu, &d32.D}, {d->lg, (N + 1) * ng, &d32.lg}, {d->ug, (N + 1) * ng, &d32.ug},
-      {d->lg_mask, (N + 1) * ng, &d32.lg_mask}, {d->ug_mask, (N + 1) * ng, &d32.ug_mask}};
+  const size_t B = (size_t)batch, N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu;
   const size_t ex = (N + 1) * nx, eu = N * nu;
   const size_t warm_e = (N + 1) * (96 + (size_t)((m.ng + 11) / 12) * 48);
   size_t floats = 2 * ex + eu;  // per QP: x, u, pi
-  for (const F& f : ins) floats += f.src ? f.e : 0;
+  fields::for_each_input(m, [&](size_t n, const auto& src) { floats += src ? n : 0; }, *d);
   // warm_start: the caller's x / u as they are on entry (the fp64 fallback starts from them)
   const size_t keep_e = st->warm_start ? ex + eu : 0;
-  const size_t need = B * (floats * sizeof(float) + (warm_e + keep_e) * sizeof(double)) + 512;
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
-  hipError_t e = hipSuccess;
-  if (need > h->mixed_bytes) {
-    if (h->mixed) hipFree(h->mixed);
-    h->mixed = nullptr;
-    h->mixed_bytes = 0;
-    e = hipMalloc(&h->mixed, need);
-    if (e != hipSuccess) {
-      hipSetDevice(prev);
-      return fail(SRBD_QP_ENOMEM, std::string("mixed-precision buffers: ") + hipGetErrorString(e));
-    }
-    h->mixed_bytes = need;
-  }
-  double* warm = reinterpret_cast<double*>(h->mixed);
+  srbd::DeviceGuard guard(h->device);
+  hipError_t e = h->mixed.reserve(B * (floats * sizeof(float) + (warm_e + keep_e) * sizeof(double)) + 512);
+  if (e != hipSuccess)
+    return fail(SRBD_QP_ENOMEM, std::string("mixed-precision buffers: ") + hipGetErrorString(e));
+  double* warm = h->mixed.as<double>();
   double* keep_x = keep_e ? warm + B * warm_e : nullptr;
   double* keep_u = keep_e ? keep_x + B * ex : nullptr;
   float* cur = reinterpret_cast<float*>(warm + B * (warm_e + keep_e));
@@ -883,12 +822,13 @@ static int mixed_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
     e = hipMemcpyAsync(keep_x, s->x, sizeof(double) * B * ex, hipMemcpyDeviceToDevice, strm);
     if (e == hipSuccess) e = hipMemcpyAsync(keep_u, s->u, sizeof(double) * B * eu, hipMemcpyDeviceToDevice, strm);
   }
-  for (const F& f : ins) {
-    if (!f.src || e != hipSuccess) continue;
-    e = srbd::launch_narrow(f.src, cur, f.e * B, strm);
-    *f.dst = cur;
-    cur += f.e * B;
-  }
+  srbd_qp_data_f32 d32{};
+  fields::for_each_input(m, [&](size_t n, const auto& src, auto& dst) {
+    if (!src || e != hipSuccess) return;
+    e = srbd::launch_narrow(src, cur, n * B, strm);
+    dst = cur;
+    cur += n * B;
+  }, *d, d32);
   srbd_qp_solution_f32 s32{};
   s32.x = cur;
   s32.u = cur + ex * B;
@@ -897,7 +837,6 @@ static int mixed_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
     e = srbd::launch_narrow(s->x, s32.x, ex * B, strm);
     if (e == hipSuccess) e = srbd::launch_narrow(s->u, s32.u, eu * B, strm);
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("mixed precision: ") + hipGetErrorString(e));
   // fp32 iterations: tolerances out of reach, so every QP runs them all (a QP that stops
   // early on NaN / min step continues cold in fp64: its iterate fails the finiteness test
@@ -912,27 +851,20 @@ static int mixed_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* st,
   // (the loop ends after the last corrector step; its application rides on the widening)
   int rc = solve_impl<float>(h, batch, &st32, &d32, &s32, strm, nullptr, 1);
   if (rc) return rc;
-  hipSetDevice(h->device);
   e = srbd::launch_gather_warm_apply(reinterpret_cast<const float*>(h->ws), h->ws_qp, m.N, m.ng, batch,
                                      s32.x, s32.u, s32.pi, s->x, s->u, s->pi, warm, strm);
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("mixed precision: ") + hipGetErrorString(e));
   srbd_qp_settings st64 = *st;
   st64.warm_start = 2;
   st64.f32_iters = 0;
-  if (!h->resc_idx) {
-    hipSetDevice(h->device);
-    e = hipMalloc(reinterpret_cast<void**>(&h->resc_idx), sizeof(int) * (2 * (size_t)h->capacity + 1));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->resc_count_host), sizeof(int));
-    hipSetDevice(prev);
-    if (e != hipSuccess) return fail(SRBD_QP_ENOMEM, std::string("fallback buffers: ") + hipGetErrorString(e));
-  }
+  e = reserve_select(h, &h->resc_idx, false);
+  if (e != hipSuccess) return fail(SRBD_QP_ENOMEM, std::string("fallback buffers: ") + hipGetErrorString(e));
   srbd_qp_solution_f64 sc = *s;
   if (!sc.status) sc.status = h->resc_idx + h->capacity;
   rc = solve_impl<double>(h, batch, &st64, d, &sc, strm, warm, 0, st->iter_max - n32);
   if (rc) return rc;
   return fallback_f64(h, batch, st, d, &sc, s, strm, 1, h->resc_idx, h->resc_idx + 2 * (size_t)h->capacity,
-                      &h->resc, &h->resc_bytes, keep_x, keep_u);
+                      h->resc, keep_x, keep_u);
 }
 
 // ---------------------------------------------------------------------------
@@ -955,11 +887,6 @@ constexpr auto kSpinBudget = std::chrono::milliseconds(2);
 constexpr int kFacFlagsMax = 256;
 // host solves whose staged bytes fit this go through the handle's pinned buffer
 constexpr size_t kPinnedMaxBytes = size_t(8) << 20;
-struct Field {
-  const void* host;
-  size_t bytes;
-  size_t off;
-};
 }  // namespace
 
 // stage_d / stage_s set (srbd_qp_host_staging_*): only lay out the pinned staging buffer for
@@ -976,104 +903,55 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
   if (rc) return rc;
   if (batch == 0) return SRBD_QP_OK;
   const srbd_qp_dims& m = h->dims;
-  const size_t B = (size_t)batch, N = (size_t)m.N, nx = (size_t)m.nx, nu = (size_t)m.nu,
-               ng = (size_t)m.ng;
-  const size_t D = sizeof(T);
-  // input fields
-  std::vector<Field> in;
-  size_t off = 0;
-  auto add = [&](const T* p, size_t n) -> size_t {
-    if (!p) return (size_t)-1;
-    size_t o = off;
-    in.push_back({p, n * D, o});
-    off += ((n * D + 255) / 256) * 256;
-    return o;
-  };
-  size_t oA = add(d->A, B * N * nx * nx), oB = add(d->B, B * N * nx * nu), ob = add(d->b, B * N * nx);
-  size_t oQ = add(d->Q, B * (N + 1) * nx * nx), oS = add(d->S, B * N * nu * nx),
-         oR = add(d->R, B * N * nu * nu);
-  size_t oq = add(d->q, B * (N + 1) * nx), orr = add(d->r, B * N * nu), ox0 = add(d->x0, B * nx);
-  size_t olbu = add(d->lbu, B * N * nu), oubu = add(d->ubu, B * N * nu),
-         olbum = add(d->lbu_mask, B * N * nu), oubum = add(d->ubu_mask, B * N * nu);
-  size_t olbx = add(d->lbx, B * (N + 1) * nx), oubx = add(d->ubx, B * (N + 1) * nx),
-         olbxm = add(d->lbx_mask, B * (N + 1) * nx), oubxm = add(d->ubx_mask, B * (N + 1) * nx);
-  size_t oC = add(d->C, B * (N + 1) * ng * nx), oD = add(d->D, B * N * ng * nu),
-         olg = add(d->lg, B * (N + 1) * ng), oug = add(d->ug, B * (N + 1) * ng),
-         olgm = add(d->lg_mask, B * (N + 1) * ng), ougm = add(d->ug_mask, B * (N + 1) * ng);
-  // outputs
-  struct OutF {
-    void* host;
-    size_t bytes;
-    size_t off;
-  };
-  std::vector<OutF> outs;
-  auto addo = [&](void* p, size_t bytes) -> size_t {
-    if (!p) return (size_t)-1;
-    size_t o = off;
-    outs.push_back({p, bytes, o});
-    off += ((bytes + 255) / 256) * 256;
-    return o;
-  };
-  size_t ox = addo(s->x, B * (N + 1) * nx * D), ou = addo(s->u, B * N * nu * D),
-         opi = addo(s->pi, B * (N + 1) * nx * D);
-  size_t oP = addo(s->P, B * (N + 1) * nx * nx * D), op = addo(s->p, B * (N + 1) * nx * D),
-         oK = addo(s->K, B * N * nu * nx * D), ok = addo(s->k, B * N * nu * D);
-  size_t ost = addo(s->status, B * sizeof(int)), oit = addo(s->iter, B * sizeof(int));
-  size_t ores = addo(s->res, B * 4 * D), oobj = addo(s->obj, B * D);
-  size_t ostat = addo(s->stat, B * srbd::kStatCols * (size_t)(st->iter_max + 2) * D);
+  const size_t B = (size_t)batch;
+  const size_t stat_rows = (size_t)(st->iter_max + 2);
+  // every non-NULL field's range of the staging buffer: inputs in [0, in_end), then outputs
+  const fields::StagePlan plan = fields::plan_stage<T>(m, B, stat_rows, *d, *s);
+  const size_t off = plan.total, in_end = plan.in_end;
+  const size_t ox = plan.x().off, ou = plan.u().off;
 
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
-  hipError_t e = hipSuccess;
-  if (off > h->stage_bytes) {
-    if (h->stage) hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    e = hipMalloc(reinterpret_cast<void**>(&h->stage), off);
-    if (e == hipSuccess) h->stage_bytes = off;
-  }
-  char* base = reinterpret_cast<char*>(h->stage);
+  srbd::DeviceGuard guard(h->device);
+  hipError_t e = h->stage.reserve(off);
+  char* base = h->stage.as<char>();
   // Small problems go through a pinned mirror of the staging buffer: the fields are
   // packed with memcpy and cross PCIe in one DMA each way (per-field pageable copies
   // cost ~10 us of driver latency apiece).  Large ones copy field by field: the
   // pageable path streams at PCIe rate with no extra host pass over the data.
-  const size_t in_end = outs.empty() ? off : outs.front().off;
   const bool small = off <= kPinnedMaxBytes;
   char* pin = nullptr;
   if (e == hipSuccess && small) {
-    if (off > h->pinned_bytes) {
+    if (off > h->pinned.bytes) {
       server_stop(h);  // (it holds pointers into the old buffer)
-      if (h->pinned) hipHostFree(h->pinned);
-      h->pinned = nullptr;
-      h->pinned_bytes = 0;
-      e = hipHostMalloc(&h->pinned, off);
-      if (e == hipSuccess) h->pinned_bytes = off;
+      e = h->pinned.reserve(off);
     }
-    pin = reinterpret_cast<char*>(h->pinned);
+    pin = h->pinned.as<char>();
   }
   if (stage_d) {
-    hipSetDevice(prev);
     if (e != hipSuccess)
       return fail(SRBD_QP_ENOMEM, std::string("host staging: ") + hipGetErrorString(e));
     if (!small) return fail(SRBD_QP_ECAPACITY, "host staging: the batch's buffers exceed the pinned staging size");
-    auto hp = [&](size_t o) -> T* { return o == (size_t)-1 ? nullptr : reinterpret_cast<T*>(pin + o); };
-    auto hi = [&](size_t o) -> int* { return o == (size_t)-1 ? nullptr : reinterpret_cast<int*>(pin + o); };
-    DataT& dd = *stage_d;
-    dd = DataT{};
-    dd.A = hp(oA); dd.B = hp(oB); dd.b = hp(ob); dd.Q = hp(oQ); dd.S = hp(oS); dd.R = hp(oR);
-    dd.q = hp(oq); dd.r = hp(orr); dd.x0 = hp(ox0);
-    dd.lbu = hp(olbu); dd.ubu = hp(oubu); dd.lbu_mask = hp(olbum); dd.ubu_mask = hp(oubum);
-    dd.lbx = hp(olbx); dd.ubx = hp(oubx); dd.lbx_mask = hp(olbxm); dd.ubx_mask = hp(oubxm);
-    dd.C = hp(oC); dd.D = hp(oD); dd.lg = hp(olg); dd.ug = hp(oug); dd.lg_mask = hp(olgm);
-    dd.ug_mask = hp(ougm);
-    SolT& ss = *stage_s;
-    ss = SolT{};
-    ss.x = hp(ox); ss.u = hp(ou); ss.pi = hp(opi); ss.P = hp(oP); ss.p = hp(op); ss.K = hp(oK);
-    ss.k = hp(ok); ss.status = hi(ost); ss.iter = hi(oit); ss.res = hp(ores); ss.obj = hp(oobj);
-    ss.stat = hp(ostat);
+    fields::stage_pointers(plan, pin, m, *stage_d, *stage_s);
     return SRBD_QP_OK;
   }
+  // the caller's buffers against the plan's ranges, in the plan's slot order: fn(host pointer,
+  // range) for every input the caller passed, fn(host pointer, range, is one of P, p, K, k) for
+  // every output
+  auto each_input = [&](auto&& fn) {
+    int i = 0;
+    fields::for_each_input(m, [&](size_t, const auto& f) {
+      const fields::StagePlan::Range& g = plan.r[i++];
+      if (f) fn(static_cast<const void*>(f), g);
+    }, *d);
+  };
+  auto each_output = [&](auto&& fn) {
+    int i = plan.n_in;
+    auto visit = [&](size_t, const auto& f) {
+      const fields::StagePlan::Range& g = plan.r[i++];
+      const void* member = &f;
+      if (f) fn(static_cast<void*>(f), g, member == &s->P || member == &s->p || member == &s->K || member == &s->k);
+    };
+    fields::for_each_solution_field(m, stat_rows, visit, visit, *s);
+  };
   // Zero copy: when the launch reads each QP's data exactly once (the single-QP kernel's
   // copy into LDS) and writes each output once, the kernel reads the pinned staging buffer
   // over PCIe and writes its outputs straight into it -- no DMA either way, one launch, one
@@ -1116,19 +994,22 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
     }
   }
   if (e == hipSuccess && small) {
-    for (const Field& f : in)
-      if (f.host != pin + f.off) std::memmove(pin + f.off, f.host, f.bytes);  // (staged in place: no copy)
+    each_input([&](const void* host, const fields::StagePlan::Range& g) {
+      if (host != pin + g.off) std::memmove(pin + g.off, host, g.bytes);  // (staged in place: no copy)
+    });
     if (!zero_copy) e = hipMemcpyAsync(base, pin, in_end, hipMemcpyHostToDevice, h->stream);
+  } else if (!small) {
+    each_input([&](const void* host, const fields::StagePlan::Range& g) {
+      if (e == hipSuccess) e = hipMemcpyAsync(base + g.off, host, g.bytes, hipMemcpyHostToDevice, h->stream);
+    });
   }
-  for (size_t i = 0; !small && e == hipSuccess && i < in.size(); ++i)
-    e = hipMemcpyAsync(base + in[i].off, in[i].host, in[i].bytes, hipMemcpyHostToDevice, h->stream);
   // warm start: x/u outputs are inputs too
   if (e == hipSuccess && st->warm_start) {
-    const size_t bx = B * (N + 1) * nx * D, bu = B * N * nu * D;
+    const size_t bx = plan.x().bytes, bu = plan.u().bytes;
     if (small) {
       if ((const void*)s->x != pin + ox) std::memmove(pin + ox, s->x, bx);
       if ((const void*)s->u != pin + ou) std::memmove(pin + ou, s->u, bu);
-      // x and u are adjacent in the staging layout (addo order, 256-byte aligned)
+      // x and u are adjacent in the staging layout (StagePlan)
       if (!zero_copy) e = hipMemcpyAsync(base + ox, pin + ox, ou + bu - ox, hipMemcpyHostToDevice, h->stream);
     } else {
       e = hipMemcpyAsync(base + ox, s->x, bx, hipMemcpyHostToDevice, h->stream);
@@ -1139,24 +1020,11 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
     // an earlier copy from the pinned buffer may still be queued: drain the stream before
     // the next call may overwrite (or free) that buffer
     hipStreamSynchronize(h->stream);
-    hipSetDevice(prev);
     return fail(SRBD_QP_EDEVICE, std::string("host->device copy: ") + hipGetErrorString(e));
   }
-  auto dp = [&](size_t o) -> T* {
-    return o == (size_t)-1 ? nullptr : reinterpret_cast<T*>(base + o);
-  };
-  auto ip = [&](size_t o) -> int* { return o == (size_t)-1 ? nullptr : reinterpret_cast<int*>(base + o); };
-  DataT dd{};
-  dd.A = dp(oA); dd.B = dp(oB); dd.b = dp(ob); dd.Q = dp(oQ); dd.S = dp(oS); dd.R = dp(oR);
-  dd.q = dp(oq); dd.r = dp(orr); dd.x0 = dp(ox0);
-  dd.lbu = dp(olbu); dd.ubu = dp(oubu); dd.lbu_mask = dp(olbum); dd.ubu_mask = dp(oubum);
-  dd.lbx = dp(olbx); dd.ubx = dp(oubx); dd.lbx_mask = dp(olbxm); dd.ubx_mask = dp(oubxm);
-  dd.C = dp(oC); dd.D = dp(oD); dd.lg = dp(olg); dd.ug = dp(oug); dd.lg_mask = dp(olgm);
-  dd.ug_mask = dp(ougm);
-  SolT ss{};
-  ss.x = dp(ox); ss.u = dp(ou); ss.pi = dp(opi); ss.P = dp(oP); ss.p = dp(op); ss.K = dp(oK);
-  ss.k = dp(ok); ss.status = ip(ost); ss.iter = ip(oit); ss.res = dp(ores); ss.obj = dp(oobj);
-  ss.stat = dp(ostat);
+  DataT dd;
+  SolT ss;
+  fields::stage_pointers(plan, base, m, dd, ss);
   // One QP that the latency kernel would solve in place: post it to the resident server
   // instead of launching (no launch, dispatch or completion-signal latency).
   bool served = false;
@@ -1197,7 +1065,6 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
     }
   }
   if (!served) {
-    hipSetDevice(prev);
     rc = solve_impl<T>(h, batch, st, &dd, &ss, nullptr);
     if (rc) {
       h->fac_arm = nullptr;
@@ -1206,14 +1073,12 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
       hipStreamSynchronize(h->stream);
       return rc;
     }
-    hipSetDevice(h->device);
   }
   h->fac_arm = nullptr;
   if (small) {
     if (e == hipSuccess && in_end < off && !zero_copy)
       e = hipMemcpyAsync(pin + in_end, base + in_end, off - in_end, hipMemcpyDeviceToHost, h->stream);
     // poll for the single-QP launch for at most kSpinBudget, then block (spin_pause above)
-    auto is_fac = [&](size_t o) { return o == oP || o == op || o == oK || o == ok; };
     bool fired = false;
     int seen = 0;  // QPs whose early-factor flag is up
     auto factors_check = [&]() {
@@ -1222,8 +1087,9 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
       while (seen < batch && f[seen]) ++seen;
       if (seen < batch) return false;
       std::atomic_thread_fence(std::memory_order_acquire);
-      for (const OutF& o : outs)
-        if (is_fac(o.off) && o.host != pin + o.off) std::memmove(o.host, pin + o.off, o.bytes);
+      each_output([&](void* host, const fields::StagePlan::Range& g, bool factor) {
+        if (factor && host != pin + g.off) std::memmove(host, pin + g.off, g.bytes);
+      });
       on_factors(ctx);
       fired = true;
       return true;
@@ -1264,17 +1130,18 @@ static int solve_host_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
       if (q != hipSuccess && q != hipErrorNotReady) e = q;
     }
     if (e == hipSuccess && !served) e = hipStreamSynchronize(h->stream);
-    for (size_t i = 0; e == hipSuccess && i < outs.size(); ++i)
-      if (outs[i].host != pin + outs[i].off && !(fired && is_fac(outs[i].off)))
-        std::memmove(outs[i].host, pin + outs[i].off, outs[i].bytes);
+    if (e == hipSuccess)
+      each_output([&](void* host, const fields::StagePlan::Range& g, bool factor) {
+        if (host != pin + g.off && !(fired && factor)) std::memmove(host, pin + g.off, g.bytes);
+      });
     if (e == hipSuccess && on_factors && !fired) on_factors(ctx);
   } else {
-    for (size_t i = 0; e == hipSuccess && i < outs.size(); ++i)
-      e = hipMemcpyAsync(outs[i].host, base + outs[i].off, outs[i].bytes, hipMemcpyDeviceToHost, h->stream);
+    each_output([&](void* host, const fields::StagePlan::Range& g, bool) {
+      if (e == hipSuccess) e = hipMemcpyAsync(host, base + g.off, g.bytes, hipMemcpyDeviceToHost, h->stream);
+    });
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && on_factors) on_factors(ctx);
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("device->host copy: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1310,56 +1177,20 @@ static int solve_soft_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
     return fail(SRBD_QP_EINVAL, "soft_x needs Zl_x, Zu_x, zl_x and zu_x");
   if (batch == 0) return SRBD_QP_OK;
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   const bool padded = dm.nx != 12 || dm.nu != 12;
-  // first-use buffers: allocated into locals, committed to the handle only when all succeeded
-  {
-    const size_t ws_need = srbd::ws_doubles_soft(dm.N) * sizeof(double) * (size_t)h->capacity;
-    const size_t sp_need = padded ? srbd::pad_soft_elems(h->capacity, dm.N) * sizeof(double) : 0;
-    const size_t pd_need = padded ? srbd::pad_elems(h->capacity, dm.N, 0) * sizeof(double) : 0;
-    void *nws = nullptr, *nsp = nullptr, *npd = nullptr;
-    hipError_t ea = hipSuccess;
-    if (ws_need > h->soft_ws_bytes) ea = hipMalloc(&nws, ws_need);
-    if (ea == hipSuccess && sp_need > h->soft_pad_bytes) ea = hipMalloc(&nsp, sp_need);
-    if (ea == hipSuccess && pd_need > h->pad_bytes) ea = hipMalloc(&npd, pd_need);
-    if (ea != hipSuccess) {
-      if (nws) hipFree(nws);
-      if (nsp) hipFree(nsp);
-      if (npd) hipFree(npd);
-      hipSetDevice(prev);
-      return fail(SRBD_QP_ENOMEM, std::string("soft-box buffers: ") + hipGetErrorString(ea));
-    }
-    if (nws) {
-      if (h->soft_ws) hipFree(h->soft_ws);
-      h->soft_ws = static_cast<double*>(nws);
-      h->soft_ws_bytes = ws_need;
-    }
-    if (nsp) {
-      if (h->soft_pad) hipFree(h->soft_pad);
-      h->soft_pad = nsp;
-      h->soft_pad_bytes = sp_need;
-    }
-    if (npd) {
-      if (h->pad) hipFree(h->pad);
-      h->pad = npd;
-      h->pad_bytes = pd_need;
-    }
-  }
+  hipError_t ea = h->soft_ws.reserve(srbd::ws_doubles_soft(dm.N) * sizeof(double) * (size_t)h->capacity);
+  if (ea == hipSuccess && padded) ea = h->soft_pad.reserve(srbd::pad_soft_elems(h->capacity, dm.N) * sizeof(double));
+  if (ea == hipSuccess && padded) ea = h->pad.reserve(srbd::pad_elems(h->capacity, dm.N, 0) * sizeof(double));
+  if (ea != hipSuccess) return fail(SRBD_QP_ENOMEM, std::string("soft-box buffers: ") + hipGetErrorString(ea));
   srbd::ProblemArgsT<double> a = build_args<double>(h, batch, st, d, s, s->status, nullptr, 0);
   a.itref_corr_max = 0;
   a.lq_fact = 0;
   srbd::SoftArgsT<double> soft;
   std::memset(&soft, 0, sizeof soft);
-  soft.soft_u = sf->soft_u; soft.Zl_u = sf->Zl_u; soft.Zu_u = sf->Zu_u; soft.zl_u = sf->zl_u;
-  soft.zu_u = sf->zu_u; soft.lls_u = sf->lls_u; soft.lus_u = sf->lus_u;
-  soft.soft_x = sf->soft_x; soft.Zl_x = sf->Zl_x; soft.Zu_x = sf->Zu_x; soft.zl_x = sf->zl_x;
-  soft.zu_x = sf->zu_x; soft.lls_x = sf->lls_x; soft.lus_x = sf->lus_x;
-  if (sl) {
-    soft.sl_u = sl->sl_u; soft.su_u = sl->su_u; soft.sl_x = sl->sl_x; soft.su_x = sl->su_x;
-  }
-  soft.sws = h->soft_ws;
+  fields::for_each_soft_input(dm, copy_pointer, *sf, soft);
+  if (sl) fields::for_each_slack_output(dm, copy_pointer, *sl, soft);
+  soft.sws = h->soft_ws.as<double>();
   soft.sws_qp = srbd::ws_doubles_soft(dm.N);
   hipError_t e = hipSuccess;
   if (s->stat)
@@ -1368,15 +1199,14 @@ static int solve_soft_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* 
   srbd::ProblemArgsT<double> run = a;
   srbd::SoftArgsT<double> srun = soft;
   if (e == hipSuccess && padded) {
-    e = srbd::pad_problem<double>(a, reinterpret_cast<double*>(h->pad), run, strm);
-    if (e == hipSuccess) e = srbd::pad_soft(a, soft, reinterpret_cast<double*>(h->soft_pad), srun, strm);
+    e = srbd::pad_problem<double>(a, h->pad.as<double>(), run, strm);
+    if (e == hipSuccess) e = srbd::pad_soft(a, soft, h->soft_pad.as<double>(), srun, strm);
   }
   if (e == hipSuccess) e = srbd::launch_ipm_soft(run, srun, strm);
   if (e == hipSuccess && padded) {
     e = srbd::unpad_solution<double>(a, run, strm);
     if (e == hipSuccess) e = srbd::unpad_slack(a, soft, srun, strm);
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1392,83 +1222,41 @@ static int solve_soft_host_impl(srbd_qp_handle h, int batch, const srbd_qp_setti
     return fail(SRBD_QP_EINVAL, "srbd_qp_solve_soft_host_f64 does not return P, p, K, k or stat");
   if (batch == 0) return SRBD_QP_OK;
   const srbd_qp_dims& dm = h->dims;
-  const size_t B = (size_t)batch, N = (size_t)dm.N, nx = (size_t)dm.nx, nu = (size_t)dm.nu, ng = (size_t)dm.ng;
-  struct Item {
-    const void* src;  // host input (NULL: output only)
-    void* dst;        // host output (NULL: input only)
-    size_t bytes;
-    void** dev;       // the device struct's field
-  };
-  std::vector<Item> items;
-  srbd_qp_data_f64 dd = *d;
-  srbd_qp_soft_f64 ds = *sf;
-  srbd_qp_solution_f64 dsol = *s;
-  srbd_qp_slack_f64 dsl{nullptr, nullptr, nullptr, nullptr};
-  if (sl) dsl = *sl;
-  auto in = [&](const double*& f, size_t elems) {
-    if (f) items.push_back(Item{f, nullptr, elems * sizeof(double), (void**)&f});
-  };
-  auto out = [&](double*& f, size_t elems, bool also_in = false) {
-    if (f) items.push_back(Item{also_in ? f : nullptr, f, elems * sizeof(double), (void**)&f});
-  };
-  in(dd.A, B * N * nx * nx); in(dd.B, B * N * nx * nu); in(dd.b, B * N * nx);
-  in(dd.Q, B * (N + 1) * nx * nx); in(dd.S, B * N * nu * nx); in(dd.R, B * N * nu * nu);
-  in(dd.q, B * (N + 1) * nx); in(dd.r, B * N * nu); in(dd.x0, B * nx);
-  in(dd.lbu, B * N * nu); in(dd.ubu, B * N * nu); in(dd.lbu_mask, B * N * nu); in(dd.ubu_mask, B * N * nu);
-  in(dd.lbx, B * (N + 1) * nx); in(dd.ubx, B * (N + 1) * nx);
-  in(dd.lbx_mask, B * (N + 1) * nx); in(dd.ubx_mask, B * (N + 1) * nx);
-  in(dd.C, B * (N + 1) * ng * nx); in(dd.D, B * N * ng * nu);
-  in(dd.lg, B * (N + 1) * ng); in(dd.ug, B * (N + 1) * ng);
-  in(dd.lg_mask, B * (N + 1) * ng); in(dd.ug_mask, B * (N + 1) * ng);
-  in(ds.soft_u, B * N * nu); in(ds.Zl_u, B * N * nu); in(ds.Zu_u, B * N * nu); in(ds.zl_u, B * N * nu);
-  in(ds.zu_u, B * N * nu); in(ds.lls_u, B * N * nu); in(ds.lus_u, B * N * nu);
-  in(ds.soft_x, B * (N + 1) * nx); in(ds.Zl_x, B * (N + 1) * nx); in(ds.Zu_x, B * (N + 1) * nx);
-  in(ds.zl_x, B * (N + 1) * nx); in(ds.zu_x, B * (N + 1) * nx); in(ds.lls_x, B * (N + 1) * nx);
-  in(ds.lus_x, B * (N + 1) * nx);
-  out(dsol.x, B * (N + 1) * nx, st->warm_start != 0); out(dsol.u, B * N * nu, st->warm_start != 0);
-  out(dsol.pi, B * (N + 1) * nx); out(dsol.res, B * 4); out(dsol.obj, B);
-  out(dsl.sl_u, B * N * nu); out(dsl.su_u, B * N * nu);
-  out(dsl.sl_x, B * (N + 1) * nx); out(dsl.su_x, B * (N + 1) * nx);
-  int *h_status = s->status, *h_iter = s->iter;
-  size_t total = 0;
-  auto round = [](size_t b) { return (b + 255) / 256 * 256; };
-  for (const Item& it : items) total += round(it.bytes);
-  const size_t int_off = total;
-  total += 2 * round(B * sizeof(int));
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipSetDevice(h->device);
+  const fields::StagePlan plan = fields::plan_stage<double>(dm, (size_t)batch, 0, *d, *s, sf, sl);
+  srbd::DeviceGuard guard(h->device);
   char* buf = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), total);
-  if (e != hipSuccess) {
-    hipSetDevice(prev);
-    return fail(SRBD_QP_ENOMEM, std::string("soft host solve buffer: ") + hipGetErrorString(e));
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), plan.total);
+  if (e != hipSuccess) return fail(SRBD_QP_ENOMEM, std::string("soft host solve buffer: ") + hipGetErrorString(e));
+  srbd_qp_data_f64 dd;
+  srbd_qp_soft_f64 ds;
+  srbd_qp_solution_f64 dsol;
+  srbd_qp_slack_f64 dsl;
+  fields::stage_pointers(plan, buf, dm, dd, dsol, &ds, sl ? &dsl : nullptr);
+  // the caller's arrays against the plan's ranges, in the plan's slot order
+  int slot = 0;
+  auto upload = [&](size_t, const auto& host) {
+    const fields::StagePlan::Range& g = plan.r[slot++];
+    if (host && e == hipSuccess) e = hipMemcpyAsync(buf + g.off, host, g.bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  auto download = [&](size_t, const auto& host) {
+    const fields::StagePlan::Range& g = plan.r[slot++];
+    if (host && e == hipSuccess) e = hipMemcpyAsync(host, buf + g.off, g.bytes, hipMemcpyDeviceToHost, h->stream);
+  };
+  fields::for_each_input(dm, upload, *d);
+  fields::for_each_soft_input(dm, upload, *sf);
+  if (st->warm_start) {  // x / u outputs are inputs too (the next slots: the solution's first two)
+    upload(0, s->x);
+    upload(0, s->u);
   }
-  size_t off = 0;
-  for (Item& it : items) {
-    *it.dev = buf + off;
-    if (e == hipSuccess && it.src)
-      e = hipMemcpyAsync(buf + off, it.src, it.bytes, hipMemcpyHostToDevice, h->stream);
-    off += round(it.bytes);
-  }
-  dsol.status = h_status ? reinterpret_cast<int*>(buf + int_off) : nullptr;
-  dsol.iter = h_iter ? reinterpret_cast<int*>(buf + int_off + round(B * sizeof(int))) : nullptr;
-  hipSetDevice(prev);
   if (e == hipSuccess) rc = solve_soft_impl(h, batch, st, &dd, &ds, &dsol, sl ? &dsl : nullptr, h->stream);
-  hipSetDevice(h->device);
   if (e == hipSuccess && rc == SRBD_QP_OK) {
-    for (Item& it : items)
-      if (e == hipSuccess && it.dst)
-        e = hipMemcpyAsync(it.dst, *it.dev, it.bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && h_status)
-      e = hipMemcpyAsync(h_status, dsol.status, B * sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && h_iter)
-      e = hipMemcpyAsync(h_iter, dsol.iter, B * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    slot = plan.n_in;
+    fields::for_each_solution_field(dm, 0, download, download, *s);
+    if (sl) fields::for_each_slack_output(dm, download, *sl);
   }
   const hipError_t es = hipStreamSynchronize(h->stream);
   if (e == hipSuccess) e = es;
   hipFree(buf);
-  hipSetDevice(prev);
   if (rc) return rc;
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("soft host solve: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
@@ -1558,11 +1346,8 @@ int srbd_qp_srbd_linearize_f64(srbd_qp_handle h, int batch, const srbd_model_par
   srbd_model_params p = *params;
   if (p.qf_scale <= 0.0) p.qf_scale = (double)d.N;
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   const hipError_t e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, *out, strm);
-  (void)hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1592,12 +1377,9 @@ int srbd_qp_srbd_linesearch_f64(srbd_qp_handle h, int batch, const srbd_model_pa
   srbd_model_params p = *params;
   if (p.qf_scale <= 0.0) p.qf_scale = (double)d.N;
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   const hipError_t e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, dx, du, alpha,
                                                     merit, converged, strm);
-  (void)hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1620,9 +1402,7 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
   int rc = srbd_qp_check_settings(settings);
   if (rc) return rc;
   if (batch == 0 || sqp_max_loop == 0) return SRBD_QP_OK;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(h->device);
+  srbd::DeviceGuard guard(h->device);
   hipStream_t strm = h->stream;
   // scratch: QP data (linearisation), x0 - x_nmpc(:,0), QP solution, loop state
   const size_t B = (size_t)h->capacity, N = (size_t)d.N;
@@ -1639,23 +1419,14 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
   const Buf bx0 = take(B * 12), bx = take(B * (N + 1) * 12), bu = take(B * N * 12),
             bpi = take(B * (N + 1) * 12);
   const Buf bint = take(B * 4 + 8);  // conv, done, status, iter (ints) + active
-  const size_t need = top * sizeof(double);
-  hipError_t e = hipSuccess;
-  if (need > h->nmpc_bytes) {
-    if (h->nmpc) (void)hipFree(h->nmpc);
-    h->nmpc = nullptr;
-    h->nmpc_bytes = 0;
-    e = hipMalloc(&h->nmpc, need);
-    if (e == hipSuccess) h->nmpc_bytes = need;
-  }
+  hipError_t e = h->nmpc.reserve(top * sizeof(double));
   if (e == hipSuccess && !h->nmpc_active_host)
     e = hipHostMalloc(reinterpret_cast<void**>(&h->nmpc_active_host), sizeof(int));
   if (e != hipSuccess) {
-    (void)hipSetDevice(prev);
     return fail(e == hipErrorOutOfMemory ? SRBD_QP_ENOMEM : SRBD_QP_EDEVICE,
                 std::string("NMPC scratch allocation failed: ") + hipGetErrorString(e));
   }
-  double* base = reinterpret_cast<double*>(h->nmpc);
+  double* base = h->nmpc.as<double>();
   auto at = [&](const Buf& b) -> double* { return b.n ? base + b.off : nullptr; };
   srbd_qp_data_f64 qd{};
   qd.A = at(bA); qd.B = at(bB); qd.b = at(bb); qd.Q = at(bQ); qd.S = at(bS); qd.R = at(bR);
@@ -1675,10 +1446,8 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
     if (e == hipSuccess)
       e = srbd::launch_nmpc_prep(batch, d.N, it, xs, x0, at(bx0), done, sqp_iter, converged, strm);
     if (e != hipSuccess) break;
-    (void)hipSetDevice(prev);
     rc = solve_impl<double>(h, batch, settings, &qd, &sol, strm);
-    if (rc) return rc;  // the caller's device is current again
-    (void)hipSetDevice(h->device);
+    if (rc) return rc;
     e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, at(bx), at(bu), alpha, nullptr,
                                      conv, strm, done);
     if (e == hipSuccess)
@@ -1689,7 +1458,6 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
     if (e == hipSuccess && *h->nmpc_active_host == 0) break;  // every robot has converged
   }
   if (e == hipSuccess) e = hipStreamSynchronize(strm);
-  (void)hipSetDevice(prev);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("NMPC loop: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
