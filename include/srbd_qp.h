@@ -26,6 +26,9 @@
  *   srbd_qp_srbd_linesearch_f64  NMPCSolver::linearSearch (NMPC_solver.cpp:149-274)
  *   srbd_qp_srbd_nmpc_f64        the SQP loop of NMPCSolver::controlLoop
  *                                (NMPC_solver.cpp:362-372) around all three.
+ *   srbd_qp_srbd_*_plan_f64      the same three with a srbd_plan_f64: a reference trajectory
+ *                                (NMPCSolver::x_ref_), a footstep plan and a contact schedule
+ *                                per robot and stage.
  *
  * ------------------------------------------------------------------------
  * Problem (per QP, stages k = 0..N), identical to hpipm::OcpQp
@@ -444,6 +447,47 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
                           const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
                           int constraints, int sqp_max_loop, double* xs, double* us,
                           const double* x0, double* alpha, int* sqp_iter, int* converged);
+
+/* Plans (additive to ABI 12): per-robot, per-stage overrides of srbd_model_params
+ * (device memory, fp64, dense).  A NULL field means "the value in srbd_model_params
+ * for every robot and stage".  One robot's x_ref block is NMPCSolver::x_ref_, the
+ * column-major 12 x (N+1) reference trajectory (NMPC_solver.cpp:67, :306, :313).
+ *   x_ref   replaces params->x_ref in the cost (q = w (x - x_ref[k]), the terminal
+ *           stage with qf_scale Qf included) and in the line search's merit phi and
+ *           gradient Jphi_x;
+ *   foot_*  replace params->foot_* at that stage wherever the model forms foot - pos:
+ *           the dynamics (all four RK4 slopes), its Jacobians A / B and the line
+ *           search's shooting defect;
+ *   fz_max  replaces params->fmax for that foot and stage in row 4 (fz <= fmax) of the
+ *           foot's twelve cone rows: the relaxed barrier in R / r, lg = -f(u) with
+ *           CONE, and the line search's merit.  With BOX_U the upper bound of that
+ *           foot's fz becomes min(u_hi[fz], fz_max).
+ * Caller's contract (device data, not checked): fz_max > fmin and fz_max > u_lo[fz];
+ * a swing foot gets a small positive limit, not 0.                               */
+typedef struct srbd_plan_f64 {
+  const double* x_ref;   /* [batch][N+1][12]  reference state per stage               */
+  const double* foot_r;  /* [batch][N][3]     right-foot position at stage k          */
+  const double* foot_l;  /* [batch][N][3]     left-foot position                      */
+  const double* fz_max;  /* [batch][N][2]     normal-force limit (right, left): the
+                          *                   contact schedule                         */
+} srbd_plan_f64;
+
+/* The three entry points above with a plan; the other arguments and their checks are
+ * the same.  plan == NULL, or a plan whose fields are all NULL, is the call without a
+ * plan: the same kernels, the same bits.  The plan's arrays are read by the launched
+ * kernels: keep them alive like xs / us.                                          */
+int srbd_qp_srbd_linearize_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                    const srbd_plan_f64* plan, int constraints, const double* xs,
+                                    const double* us, const srbd_qp_data_f64* out, void* stream);
+int srbd_qp_srbd_linesearch_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                     const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                                     double* xs, double* us, const double* dx, const double* du,
+                                     double* alpha, double* merit, int* converged, void* stream);
+int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                               const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                               const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                               double* xs, double* us, const double* x0, double* alpha,
+                               int* sqp_iter, int* converged);
 
 /* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,

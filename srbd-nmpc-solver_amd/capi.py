@@ -104,6 +104,56 @@ class LsParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("theta_max", "theta_min", "eta", "beta_phi",
                                          "beta_theta", "beta_alpha", "alpha_min")]
 
+
+
+class PlanStruct(C.Structure):
+    """srbd_plan_f64: device pointers, NULL = the value in srbd_model_params."""
+    _fields_ = [(n, _dp) for n in ("x_ref", "foot_r", "foot_l", "fz_max")]
+
+
+class Plan:
+    """Per-robot, per-stage overrides of ModelParams for srbd_linearize / srbd_linesearch /
+    srbd_nmpc (srbd_plan_f64): torch fp64 device tensors, each optional.
+
+    x_ref  [B][N+1][12]  reference state per stage (one robot's block is an Eigen
+                         MatrixXd(12, N+1), the reference's x_ref_)
+    foot_r [B][N][3]     right-foot position at stage k
+    foot_l [B][N][3]     left-foot position
+    fz_max [B][N][2]     normal-force limit (right, left): the contact schedule; a swing
+                         foot gets a small positive limit
+
+    The holder keeps the tensors alive; the calls check dtype, contiguity and shapes."""
+    FIELDS = {"x_ref": (1, 12), "foot_r": (0, 3), "foot_l": (0, 3), "fz_max": (0, 2)}
+
+    def __init__(self, x_ref=None, foot_r=None, foot_l=None, fz_max=None):
+        self.x_ref, self.foot_r, self.foot_l, self.fz_max = x_ref, foot_r, foot_l, fz_max
+
+    def struct(self, B: int, N: int, device=None) -> PlanStruct:
+        """The C struct for a batch of B robots over N stages; ValueError on a mismatch."""
+        import torch
+        ps = PlanStruct()
+        for name, (extra, width) in self.FIELDS.items():
+            t = getattr(self, name)
+            if t is None:
+                continue
+            want = (int(B), int(N) + extra, width)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"plan.{name} must be a torch.float64 tensor")
+            if tuple(t.shape) != want:
+                raise ValueError(f"plan.{name} has shape {tuple(t.shape)}, expected {want}")
+            if not t.is_contiguous():
+                raise ValueError(f"plan.{name} must be contiguous")
+            if device is not None and t.device != device:
+                raise ValueError(f"plan.{name} is on {t.device}, the trajectories on {device}")
+            setattr(ps, name, t.data_ptr())
+        return ps
+
+
+def _plan_ref(plan: Optional["Plan"], B: int, N: int, device):
+    """byref(PlanStruct) or None (a NULL plan) for the _plan_ entry points."""
+    return None if plan is None else C.byref(plan.struct(B, N, device))
+
+
 _lib = None
 
 
@@ -206,6 +256,20 @@ def lib():
                                             C.POINTER(LsParams), C.POINTER(Settings), C.c_int,
                                             C.c_int] + [C.c_void_p] * 6
         L.srbd_qp_srbd_nmpc_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_srbd_nmpc_plan_f64"):  # plans (older builds: A/B runs)
+            L.srbd_qp_srbd_linearize_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                          C.POINTER(PlanStruct), C.c_int, C.c_void_p,
+                                                          C.c_void_p, C.POINTER(Data), C.c_void_p]
+            L.srbd_qp_srbd_linearize_plan_f64.restype = C.c_int
+            L.srbd_qp_srbd_linesearch_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                           C.POINTER(PlanStruct),
+                                                           C.POINTER(LsParams)] + [C.c_void_p] * 8
+            L.srbd_qp_srbd_linesearch_plan_f64.restype = C.c_int
+            L.srbd_qp_srbd_nmpc_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                     C.POINTER(PlanStruct), C.POINTER(LsParams),
+                                                     C.POINTER(Settings), C.c_int,
+                                                     C.c_int] + [C.c_void_p] * 6
+            L.srbd_qp_srbd_nmpc_plan_f64.restype = C.c_int
         L.srbd_qp_abi_version.argtypes = []
         L.srbd_qp_abi_version.restype = C.c_int
         _lib = L
@@ -500,27 +564,40 @@ def model_params(p) -> ModelParams:
     return m
 
 
+def _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream):
+    """srbd_qp_srbd_linearize_f64, or the _plan_ entry point when a plan is given."""
+    tail = (SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()), C.c_void_p(us.data_ptr()),
+            C.byref(data), C.c_void_p(stream or None))
+    if plan_ref is None:
+        check(lib().srbd_qp_srbd_linearize_f64(handle.ptr, int(B), C.byref(p), *tail),
+              "srbd_qp_srbd_linearize_f64")
+    else:
+        check(lib().srbd_qp_srbd_linearize_plan_f64(handle.ptr, int(B), C.byref(p), plan_ref, *tail),
+              "srbd_qp_srbd_linearize_plan_f64")
+
+
 def srbd_linearize(handle: Handle, xs, us, constraints: str = "none",
-                   params: Optional[ModelParams] = None, stream: int = 0, out=None):
+                   params: Optional[ModelParams] = None, stream: int = 0, out=None,
+                   plan: Optional[Plan] = None):
     """Device-side prepareQpStructures: linearise SRBD trajectories xs [B][N+1][12],
     us [B][N][12] (torch fp64 device tensors) into the solver's input buffers.
     Asynchronous on the handle's stream: keep xs / us alive (and do not reuse
     their memory from another stream) until that stream has finished.
+    `plan` (a Plan) overrides the reference, the feet and the force limits per robot and
+    stage; its tensors must stay alive like xs / us.
     Returns (dict of device tensors in the C-ABI layout, Data)."""
     import torch
     B, N1, _ = xs.shape
     N = N1 - 1
     dev = xs.device
+    plan_ref = _plan_ref(plan, B, N, dev)
     f = dict(dtype=torch.float64, device=dev)
     if out is not None:  # caller-owned buffers from a previous call (no allocation)
         t = out
         data = Data(**{k: _tensor_ptr(t.get(k)) or None for k in DATA_FIELDS})
         p = params or default_model_params()
         o = _order_before(handle, stream, True)
-        check(lib().srbd_qp_srbd_linearize_f64(handle.ptr, int(B), C.byref(p),
-                                               SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()),
-                                               C.c_void_p(us.data_ptr()), C.byref(data),
-                                               C.c_void_p(stream or None)), "srbd_qp_srbd_linearize_f64")
+        _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream)
         _order_after(o)
         return t, data
     t = {"A": torch.empty(B, N, 144, **f), "B": torch.empty(B, N, 144, **f),
@@ -537,10 +614,7 @@ def srbd_linearize(handle: Handle, xs, us, constraints: str = "none",
     data = Data(**{k: _tensor_ptr(t.get(k)) or None for k in DATA_FIELDS})
     p = params or default_model_params()
     o = _order_before(handle, stream, True)
-    check(lib().srbd_qp_srbd_linearize_f64(handle.ptr, int(B), C.byref(p), SRBD_CONSTRAINTS[constraints],
-                                           C.c_void_p(xs.data_ptr()), C.c_void_p(us.data_ptr()),
-                                           C.byref(data), C.c_void_p(stream or None)),
-          "srbd_qp_srbd_linearize_f64")
+    _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream)
     _order_after(o)
     return t, data
 
@@ -552,36 +626,45 @@ def default_linesearch() -> LsParams:
 
 
 def srbd_linesearch(handle: Handle, xs, us, dx, du, alpha, params: Optional[ModelParams] = None,
-                    ls: Optional[LsParams] = None, stream: int = 0):
+                    ls: Optional[LsParams] = None, stream: int = 0, plan: Optional[Plan] = None):
     """Device filter line search (NMPCSolver::linearSearch) on a batch: xs/us
     (torch fp64, in place), dx/du the QP step, alpha [B] in/out.  Returns
-    (merit [B,3] = phi, theta, dphi; converged [B]) device tensors."""
+    (merit [B,3] = phi, theta, dphi; converged [B]) device tensors.  `plan`: as in
+    srbd_linearize."""
     import torch
     B = xs.shape[0]
+    plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
     merit = torch.empty(B, 3, dtype=torch.float64, device=xs.device)
     conv = torch.empty(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
     lp = ls or default_linesearch()
     ptr = lambda t: C.c_void_p(t.data_ptr())
     o = _order_before(handle, stream, True)
-    check(lib().srbd_qp_srbd_linesearch_f64(handle.ptr, int(B), C.byref(p), C.byref(lp), ptr(xs),
-                                            ptr(us), ptr(dx), ptr(du), ptr(alpha), ptr(merit),
-                                            ptr(conv), C.c_void_p(stream or None)),
-          "srbd_qp_srbd_linesearch_f64")
+    tail = (C.byref(lp), ptr(xs), ptr(us), ptr(dx), ptr(du), ptr(alpha), ptr(merit), ptr(conv),
+            C.c_void_p(stream or None))
+    if plan_ref is None:
+        check(lib().srbd_qp_srbd_linesearch_f64(handle.ptr, int(B), C.byref(p), *tail),
+              "srbd_qp_srbd_linesearch_f64")
+    else:
+        check(lib().srbd_qp_srbd_linesearch_plan_f64(handle.ptr, int(B), C.byref(p), plan_ref, *tail),
+              "srbd_qp_srbd_linesearch_plan_f64")
     _order_after(o)
     return merit, conv
 
 
 def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
               settings: Optional[Dict] = None, sqp_max_loop: int = 15,
-              params: Optional[ModelParams] = None, ls: Optional[LsParams] = None):
+              params: Optional[ModelParams] = None, ls: Optional[LsParams] = None,
+              plan: Optional[Plan] = None):
     """The SQP loop of NMPCSolver::controlLoop (NMPC_solver.cpp:362-372) for a batch
     of robots on the device (srbd_qp_srbd_nmpc_f64): xs [B][N+1][12], us [B][N][12]
     (torch fp64, updated in place), x0 [B][12], alpha [B] (in place, the persistent
     alpha_ of NMPC_solver.h:104).  Returns (sqp_iter [B], converged [B]) int32
-    device tensors.  Synchronous."""
+    device tensors.  Synchronous.  `plan` (a Plan): each robot's reference trajectory,
+    footstep plan and contact schedule over the horizon (srbd_qp_srbd_nmpc_plan_f64)."""
     import torch
     B = xs.shape[0]
+    plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
     it = torch.zeros(B, dtype=torch.int32, device=xs.device)
     conv = torch.zeros(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
@@ -589,9 +672,12 @@ def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
     s = settings_struct(settings)
     ptr = lambda t: C.c_void_p(t.data_ptr())
     o = _order_before(handle, 0, True)
-    check(lib().srbd_qp_srbd_nmpc_f64(handle.ptr, int(B), C.byref(p), C.byref(lp), C.byref(s),
-                                      SRBD_CONSTRAINTS[constraints], int(sqp_max_loop), ptr(xs),
-                                      ptr(us), ptr(x0), ptr(alpha), ptr(it), ptr(conv)),
-          "srbd_qp_srbd_nmpc_f64")
+    tail = (C.byref(lp), C.byref(s), SRBD_CONSTRAINTS[constraints], int(sqp_max_loop), ptr(xs),
+            ptr(us), ptr(x0), ptr(alpha), ptr(it), ptr(conv))
+    if plan_ref is None:
+        check(lib().srbd_qp_srbd_nmpc_f64(handle.ptr, int(B), C.byref(p), *tail), "srbd_qp_srbd_nmpc_f64")
+    else:
+        check(lib().srbd_qp_srbd_nmpc_plan_f64(handle.ptr, int(B), C.byref(p), plan_ref, *tail),
+              "srbd_qp_srbd_nmpc_plan_f64")
     _order_after(o)
     return it, conv

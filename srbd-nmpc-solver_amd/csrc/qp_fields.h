@@ -71,6 +71,14 @@ constexpr void for_each_slack_output(const srbd_qp_dims& m, F&& f, S&... s) {
   f(us, s.sl_u...); f(us, s.su_u...); f(xs, s.sl_x...); f(xs, s.su_x...);
 }
 
+// The 4 arrays of srbd_plan_f64 (per-robot, per-stage overrides of srbd_model_params; 12 x 12
+// stages: the SRBD entry points need nx = nu = 12).
+template <class F, class... S>
+constexpr void for_each_plan_field(const srbd_qp_dims& m, F&& f, S&... s) {
+  const size_t N = (size_t)m.N;
+  f((N + 1) * 12, s.x_ref...); f(N * 3, s.foot_r...); f(N * 3, s.foot_l...); f(N * 2, s.fz_max...);
+}
+
 namespace detail {
 template <class DataT>
 constexpr size_t count_inputs() {
@@ -98,12 +106,19 @@ constexpr size_t count_slack_outputs() {
   for_each_slack_output(srbd_qp_dims{}, [&n](size_t, auto&) { ++n; }, s);
   return n;
 }
+constexpr size_t count_plan_fields() {
+  size_t n = 0;
+  srbd_plan_f64 s{};
+  for_each_plan_field(srbd_qp_dims{}, [&n](size_t, auto&) { ++n; }, s);
+  return n;
+}
 }  // namespace detail
 
 constexpr size_t kDataFields = detail::count_inputs<srbd_qp_data_f64>();
 constexpr size_t kSolutionFields = detail::count_solution_fields<srbd_qp_solution_f64>();
 constexpr size_t kSoftFields = detail::count_soft_inputs();
 constexpr size_t kSlackFields = detail::count_slack_outputs();
+constexpr size_t kPlanFields = detail::count_plan_fields();
 static_assert(kDataFields == sizeof(srbd_qp_data_f64) / sizeof(void*) &&
                   kDataFields == sizeof(srbd_qp_data_f32) / sizeof(void*),
               "for_each_input must visit every member of srbd_qp_data_*");
@@ -114,6 +129,9 @@ static_assert(kSoftFields == sizeof(srbd_qp_soft_f64) / sizeof(void*),
               "for_each_soft_input must visit every member of srbd_qp_soft_f64");
 static_assert(kSlackFields == sizeof(srbd_qp_slack_f64) / sizeof(void*),
               "for_each_slack_output must visit every member of srbd_qp_slack_f64");
+
+static_assert(kPlanFields == sizeof(srbd_plan_f64) / sizeof(void*),
+              "for_each_plan_field must visit every member of srbd_plan_f64");
 
 // ---------------------------------------------------------------------------
 // The staging layout of a host-buffer call: one buffer, every non-NULL field of the call at a

@@ -27,6 +27,7 @@ __device__ __forceinline__ void st_nt(double2* p, double x, double y) {
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 
 namespace srbd {
 namespace {
@@ -129,6 +130,56 @@ __device__ M3 djl(const V3& v, int a) {
   return lin(1.0, d, v.v[a], base);
 }
 
+// A plan (srbd_plan_f64) overrides four of the model's constants per robot and stage: the
+// reference state, the two foot positions and the normal-force limit of each foot.  Kernels
+// and helpers that read them take a `bool PLAN`: false is the code without plans (the values
+// are Model::p's, StageVals is empty), true loads them from the plan's arrays, a NULL array
+// falling back to Model::p on a wave-uniform branch.
+struct NoPlan {};
+template <bool PLAN>
+using PlanArgs = std::conditional_t<PLAN, srbd_plan_f64, NoPlan>;
+
+// The foot positions and force limits of one (robot, stage).  With a plan they are loaded once
+// per stage and stay in registers: Model::f runs four times per stage.
+template <bool PLAN>
+struct StageVals {
+  __device__ __forceinline__ double foot_r(const srbd_model_params& p, int i) const { return p.foot_r[i]; }
+  __device__ __forceinline__ double foot_l(const srbd_model_params& p, int i) const { return p.foot_l[i]; }
+  __device__ __forceinline__ double fz_max(const srbd_model_params& p, int) const { return p.fmax; }
+};
+template <>
+struct StageVals<true> {
+  double fr[3], fl[3], fz[2];
+  __device__ __forceinline__ double foot_r(const srbd_model_params&, int i) const { return fr[i]; }
+  __device__ __forceinline__ double foot_l(const srbd_model_params&, int i) const { return fl[i]; }
+  __device__ __forceinline__ double fz_max(const srbd_model_params&, int leg) const { return fz[leg]; }
+};
+// t = qp * N + k: rows t of foot_r / foot_l ([batch][N][3]) and fz_max ([batch][N][2])
+template <bool PLAN>
+__device__ __forceinline__ StageVals<PLAN> load_stage(const srbd_model_params& p, const PlanArgs<PLAN>& pl,
+                                                      size_t t) {
+  StageVals<PLAN> s;
+  if constexpr (PLAN) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      s.fr[i] = pl.foot_r ? pl.foot_r[t * 3 + i] : p.foot_r[i];
+      s.fl[i] = pl.foot_l ? pl.foot_l[t * 3 + i] : p.foot_l[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) s.fz[i] = pl.fz_max ? pl.fz_max[t * 2 + i] : p.fmax;
+  }
+  return s;
+}
+// x_ref of element e = (qp * (N + 1) + k) * 12 + i of the [batch][N+1][12] arrays
+template <bool PLAN>
+__device__ __forceinline__ double x_ref_at(const srbd_model_params& p, const PlanArgs<PLAN>& pl, size_t e,
+                                           int i) {
+  if constexpr (PLAN) {
+    if (pl.x_ref) return pl.x_ref[e];
+  }
+  return p.x_ref[i];
+}
+
 struct Model {
   srbd_model_params p;
   __device__ double ac(int c, int j) const {
@@ -155,7 +206,8 @@ struct Model {
     return r == 4 ? p.fmax : (r == 5 ? -p.fmin : 0.0);
   }
   // continuous dynamics f(x, u) (GetContinuousDynamic)
-  __device__ void f(const double* x, const double* u, double* dx) const {
+  template <class St>
+  __device__ void f(const St& s, const double* x, const double* u, double* dx) const {
     const V3 r = seg(x, 0), l = seg(x, 3), pos = seg(x, 6);
     const M3 R = expm(r), Jlt = jlt(r);
     const M3 Lb = [&] {
@@ -166,8 +218,8 @@ struct Model {
     const M3 RLR = mul(mul(R, Lb), tr(R));
     const V3 w = mv(RLR, l);
     const V3 dr = mv(Jlt, w);
-    const V3 p0{{p.foot_r[0] - pos.v[0], p.foot_r[1] - pos.v[1], p.foot_r[2] - pos.v[2]}};
-    const V3 p1{{p.foot_l[0] - pos.v[0], p.foot_l[1] - pos.v[1], p.foot_l[2] - pos.v[2]}};
+    const V3 p0{{s.foot_r(p, 0) - pos.v[0], s.foot_r(p, 1) - pos.v[1], s.foot_r(p, 2) - pos.v[2]}};
+    const V3 p1{{s.foot_l(p, 0) - pos.v[0], s.foot_l(p, 1) - pos.v[1], s.foot_l(p, 2) - pos.v[2]}};
     const V3 t0 = mv(skew(p0), seg(u, 0)), t1 = mv(skew(p1), seg(u, 6));
     for (int i = 0; i < 3; ++i) {
       dx[i] = dr.v[i];
@@ -180,8 +232,9 @@ struct Model {
   // jfx[0:3,0:3] = J00, jfx[0:3,3:6] = J01, jfx[3:6,6:9] = [f0 + f1]x,
   // jfx[6:9,9:12] = I; jfu[3:6,0:3] = [p0]x, jfu[3:6,6:9] = [p1]x,
   // jfu[3:6,3:6] = jfu[3:6,9:12] = I, jfu[9:12,0:3] = jfu[9:12,6:9] = I / m
-  __device__ void jac_blocks(const double* x, const double* u, M3& J00, M3& J01, M3& Sf, M3& S0,
-                             M3& S1) const {
+  template <class St>
+  __device__ void jac_blocks(const St& s, const double* x, const double* u, M3& J00, M3& J01, M3& Sf,
+                             M3& S0, M3& S1) const {
     const V3 r = seg(x, 0), l = seg(x, 3), pos = seg(x, 6);
     const M3 R = expm(r), Jlt = jlt(r);
     M3 Lb = zero3();
@@ -196,8 +249,8 @@ struct Model {
     }
     J01 = mul(Jlt, RLR);
     Sf = skew(V3{{u[0] + u[6], u[1] + u[7], u[2] + u[8]}});
-    S0 = skew(V3{{p.foot_r[0] - pos.v[0], p.foot_r[1] - pos.v[1], p.foot_r[2] - pos.v[2]}});
-    S1 = skew(V3{{p.foot_l[0] - pos.v[0], p.foot_l[1] - pos.v[1], p.foot_l[2] - pos.v[2]}});
+    S0 = skew(V3{{s.foot_r(p, 0) - pos.v[0], s.foot_r(p, 1) - pos.v[1], s.foot_r(p, 2) - pos.v[2]}});
+    S1 = skew(V3{{s.foot_l(p, 0) - pos.v[0], s.foot_l(p, 1) - pos.v[1], s.foot_l(p, 2) - pos.v[2]}});
   }
   // relaxed log barrier (Barrier, :262-295): db, ddb
   __device__ void barrier(double v, double& db, double& ddb) const {
@@ -217,6 +270,9 @@ struct LinArgs {
   srbd_qp_data_f64 out;  // device pointers to fill (const dropped below)
   double qf_scale;
 };
+// with a plan, its four pointers follow the block
+template <bool PLAN>
+struct LinArgsT : LinArgs, PlanArgs<PLAN> {};
 
 // Per-stage descriptor of the matrices a (QP, stage) thread hands to its wave: the
 // nonzero 3x3 Jacobian blocks and the friction-barrier R (diagonal + 4 off-diagonal pairs
@@ -290,7 +346,10 @@ __device__ __forceinline__ double r_at(const double* d, int i, int j) {
 // blocks, barrier) in registers, the per-stage vectors (b, r, bounds / cone rows) stored
 // by the thread, the matrices through the wave's descriptors.  Q, q (diagonal cost) and
 // S (= 0) are written by srbd_lin_cost_kernel / a memset.
-__global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, LinArgs a) {
+// With a plan, the thread reads its stage's feet and force limits at t * 3 and t * 2: adjacent
+// threads, adjacent memory.
+template <bool PLAN>
+__global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, LinArgsT<PLAN> a) {
   __shared__ double desc[kLinThreads * kDesc];
   const int N = a.N;
   const long long nst_all = (long long)a.batch * N;
@@ -304,19 +363,20 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
     const double* x = a.xs + ((size_t)qp * (N + 1) + k) * 12;
     const double* u = a.us + (size_t)t * 12;
     const double* xn = x + 12;
+    const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)t);
     // ---- shooting dynamics (GetShootingDynamic, SRBD_model.cpp:178-235): b = RK4(x, u) - x_next ----
     {
       double k1[12], k2[12], k3[12], k4[12], xt[12];
-      m.f(x, u, k1);
+      m.f(sv, x, u, k1);
 #pragma unroll
       for (int i = 0; i < 12; ++i) xt[i] = x[i] + 0.5 * dt * k1[i];
-      m.f(xt, u, k2);
+      m.f(sv, xt, u, k2);
 #pragma unroll
       for (int i = 0; i < 12; ++i) xt[i] = x[i] + 0.5 * dt * k2[i];
-      m.f(xt, u, k3);
+      m.f(sv, xt, u, k3);
 #pragma unroll
       for (int i = 0; i < 12; ++i) xt[i] = x[i] + dt * k3[i];
-      m.f(xt, u, k4);
+      m.f(sv, xt, u, k4);
       double* b = const_cast<double*>(a.out.b) + (size_t)t * 12;
 #pragma unroll
       for (int i = 0; i < 12; ++i)
@@ -325,7 +385,7 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
     // ---- Jacobian blocks (A = I + dt jfx, B = dt jfu) into the descriptor ----
     {
       M3 J00, J01, Sf, S0, S1;
-      m.jac_blocks(x, u, J00, J01, Sf, S0, S1);
+      m.jac_blocks(sv, x, u, J00, J01, Sf, S0, S1);
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -336,8 +396,8 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         dsc[kDFs + i] = u[i] + u[6 + i];
-        dsc[kDP0 + i] = p.foot_r[i] - x[6 + i];
-        dsc[kDP1 + i] = p.foot_l[i] - x[6 + i];
+        dsc[kDP0 + i] = sv.foot_r(p, i) - x[6 + i];
+        dsc[kDP1 + i] = sv.foot_l(p, i) - x[6 + i];
       }
     }
     // ---- friction cone (GetConstrain :237-260, two nonzeros per row) as a barrier in the cost
@@ -359,7 +419,7 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
       v[1] = -fy + mu * fz;
       v[2] = fx + mu * fz;
       v[3] = fy + mu * fz;
-      v[4] = -fz + p.fmax;
+      v[4] = -fz + sv.fz_max(p, leg);
       v[5] = fz - p.fmin;
       v[6] = Lx * fz - ty;
       v[7] = Lx * fz + ty;
@@ -403,7 +463,10 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
 #pragma unroll
       for (int i = 0; i < 12; ++i) {
         lbu[i] = p.u_lo[i] - u[i];
-        ubu[i] = p.u_hi[i] - u[i];
+        if constexpr (PLAN)  // the contact schedule caps each foot's fz
+          ubu[i] = (i % 6 == 2 ? fmin(p.u_hi[i], sv.fz_max(p, i / 6)) : p.u_hi[i]) - u[i];
+        else
+          ubu[i] = p.u_hi[i] - u[i];
       }
     } else if (a.mode == 2) {  // lg <= Ac du with lg = -f(u) (du keeps f(u + du) >= 0)
       const size_t o = ((size_t)qp * (N + 1) + k) * 24;
@@ -445,7 +508,9 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
 // Q = diag(w) and q = diag(w) (x - x_ref) on every stage k <= N (w = Q, or qf_scale Qf at
 // N; prepareQpStructures, NMPC_solver.cpp:286-313), element-wise and coalesced; with the
 // cone, the terminal stage's rows are absent (masked).
-__global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgs a) {
+// With a plan, x_ref is read at the same element index e as xs.
+template <bool PLAN>
+__global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PLAN> a) {
   const srbd_model_params& p = m.p;
   const int N = a.N;
   const long long nq2 = (long long)a.batch * (N + 1) * 72;  // double2 of Q
@@ -465,7 +530,7 @@ __global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgs a) 
     const int i = (int)(e - blk * 12), k = (int)(blk % (N + 1));
     const double* w = k < N ? p.Q : p.Qf;
     const double sc = k < N ? 1.0 : a.qf_scale;
-    const_cast<double*>(a.out.q)[e] = sc * w[i] * (a.xs[e] - p.x_ref[i]);
+    const_cast<double*>(a.out.q)[e] = sc * w[i] * (a.xs[e] - x_ref_at<PLAN>(p, a, (size_t)e, i));
   } else if (a.mode == 2 && g < nq2 + nq + (long long)a.batch * 24) {
     const long long e = g - nq2 - nq;
     const long long qp = e / 24;
@@ -501,10 +566,14 @@ struct LsArgs {
   double qf_scale;
   const int* done;  // optional: robots whose SQP loop has stopped are left untouched
 };
+template <bool PLAN>
+struct LsArgsT : LsArgs, PlanArgs<PLAN> {};
 
 // the 24 friction-cone / torque-limit rows f(u) of GetConstrain (SRBD_model.cpp:237-260,
 // R_f = I), two nonzeros each: the explicit form of bc(c) + sum_j ac(c, j) u_j
-__device__ __forceinline__ void cone_rows(const srbd_model_params& p, const double* u, double* v) {
+template <class St>
+__device__ __forceinline__ void cone_rows(const srbd_model_params& p, const St& s, const double* u,
+                                          double* v) {
 #pragma unroll
   for (int leg = 0; leg < 2; ++leg) {
     const int o = 6 * leg;
@@ -514,7 +583,7 @@ __device__ __forceinline__ void cone_rows(const srbd_model_params& p, const doub
     w[1] = -fy + p.mu * fz;
     w[2] = fx + p.mu * fz;
     w[3] = fy + p.mu * fz;
-    w[4] = -fz + p.fmax;
+    w[4] = -fz + s.fz_max(p, leg);
     w[5] = fz - p.fmin;
     w[6] = p.Lfx * fz - ty;
     w[7] = p.Lfx * fz + ty;
@@ -544,7 +613,9 @@ __device__ __forceinline__ void cone_grad(const srbd_model_params& p, const doub
 // grad, the directional derivative dx'Jphi_x + du'Jphi_u.  RK4 through one call site of
 // the model (a loop over the four slopes) and the cone rows from their sparsity: a small
 // register footprint for this latency-bound kernel.
-__device__ void stage_merit(const Model& m, const LsArgs& a, int qp, int k, double al, bool grad,
+// With a plan the stage's rows are loaded here, once for the four slopes.
+template <bool PLAN>
+__device__ void stage_merit(const Model& m, const LsArgsT<PLAN>& a, int qp, int k, double al, bool grad,
                             double& phi, double& theta, double& dphi) {
   const srbd_model_params& p = m.p;
   const int N = a.N;
@@ -557,7 +628,7 @@ __device__ void stage_merit(const Model& m, const LsArgs& a, int qp, int k, doub
   const double sc = k < N ? 1.0 : a.qf_scale;
   #pragma unroll
   for (int i = 0; i < 12; ++i) {
-    const double e = xa[i] - p.x_ref[i];
+    const double e = xa[i] - x_ref_at<PLAN>(p, a, ((size_t)qp * (N + 1) + k) * 12 + i, i);
     phi += 0.5 * sc * w[i] * e * e;
     if (grad) dphi += dx[i] * sc * w[i] * e;
   }
@@ -566,6 +637,7 @@ __device__ void stage_merit(const Model& m, const LsArgs& a, int qp, int k, doub
   const double* du = a.du + ((size_t)qp * N + k) * 12;
   const double* xn = a.xs + ((size_t)qp * (N + 1) + k + 1) * 12;
   const double* dxn = a.dx + ((size_t)qp * (N + 1) + k + 1) * 12;
+  const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)qp * N + k);
   double ua[12];
   #pragma unroll
   for (int i = 0; i < 12; ++i) ua[i] = u[i] + al * du[i];
@@ -579,7 +651,7 @@ __device__ void stage_merit(const Model& m, const LsArgs& a, int qp, int k, doub
   }
 #pragma unroll 1
   for (int s = 0; s < 4; ++s) {
-    m.f(xt, ua, kk);
+    m.f(sv, xt, ua, kk);
     const double wt = (s == 0 || s == 3) ? 1.0 : 2.0;
     const double h = s < 2 ? 0.5 * dt : dt;
     #pragma unroll
@@ -596,7 +668,7 @@ __device__ void stage_merit(const Model& m, const LsArgs& a, int qp, int k, doub
   }
   // input cost: relaxed barrier of the friction cone + 0.5 u'R u
   double v[24];
-  cone_rows(p, ua, v);
+  cone_rows(p, sv, ua, v);
   double ju[12], db[24];
   #pragma unroll
   for (int i = 0; i < 12; ++i) {
@@ -622,7 +694,9 @@ __device__ void stage_merit(const Model& m, const LsArgs& a, int qp, int k, doub
   }
 }
 
-__global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgs a) {
+// With a plan, lane l reads the plan rows of its own stages l, l + 32, ...
+template <bool PLAN>
+__global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PLAN> a) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int qp = gid / kLsGroup, lane = gid % kLsGroup;
   if (qp >= a.batch) return;
@@ -631,7 +705,7 @@ __global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgs a) 
   const srbd_linesearch_params& ls = a.ls;
   // merit at the current iterate
   double phi = 0.0, theta = 0.0, dphi = 0.0;
-  for (int k = lane; k <= N; k += kLsGroup) stage_merit(m, a, qp, k, 0.0, true, phi, theta, dphi);
+  for (int k = lane; k <= N; k += kLsGroup) stage_merit<PLAN>(m, a, qp, k, 0.0, true, phi, theta, dphi);
   phi = gsum32(phi);
   theta = gsum32(theta);
   dphi = gsum32(dphi);
@@ -639,7 +713,7 @@ __global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgs a) 
   double accepted = -1.0;  // accepted step length, -1: none
   while (alpha > ls.alpha_min) {
     double pa = 0.0, ta = 0.0, unused = 0.0;
-    for (int k = lane; k <= N; k += kLsGroup) stage_merit(m, a, qp, k, alpha, false, pa, ta, unused);
+    for (int k = lane; k <= N; k += kLsGroup) stage_merit<PLAN>(m, a, qp, k, alpha, false, pa, ta, unused);
     pa = gsum32(pa);
     ta = gsum32(ta);
     bool ok;
@@ -679,19 +753,33 @@ __global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgs a) 
   }
 }
 
+// the PLAN kernels run only when the plan overrides something
+bool plan_given(const srbd_plan_f64* plan) {
+  return plan && (plan->x_ref || plan->foot_r || plan->foot_l || plan->fz_max);
+}
+
 }  // namespace
 
 hipError_t launch_srbd_linesearch(const srbd_model_params& p, const srbd_linesearch_params& ls,
                                   int batch, int N, double* xs, double* us, const double* dx,
                                   const double* du, double* alpha, double* merit, int* converged,
-                                  hipStream_t stream, const int* done) {
+                                  hipStream_t stream, const int* done, const srbd_plan_f64* plan) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
-  LsArgs a{batch, N, xs, us, dx, du, alpha, merit, converged, ls, p.qf_scale, done};
+  const LsArgs a{batch, N, xs, us, dx, du, alpha, merit, converged, ls, p.qf_scale, done};
   const long long n = (long long)batch * kLsGroup;
   const int threads = 64;
-  hipLaunchKernelGGL(srbd_linesearch_kernel, dim3((unsigned)((n + threads - 1) / threads)),
-                     dim3(threads), 0, stream, m, a);
+  const dim3 grid((unsigned)((n + threads - 1) / threads));
+  if (plan_given(plan)) {
+    LsArgsT<true> ap;
+    static_cast<LsArgs&>(ap) = a;
+    static_cast<srbd_plan_f64&>(ap) = *plan;
+    hipLaunchKernelGGL(srbd_linesearch_kernel<true>, grid, dim3(threads), 0, stream, m, ap);
+  } else {
+    LsArgsT<false> an;
+    static_cast<LsArgs&>(an) = a;
+    hipLaunchKernelGGL(srbd_linesearch_kernel<false>, grid, dim3(threads), 0, stream, m, an);
+  }
   return hipGetLastError();
 }
 
@@ -752,20 +840,31 @@ hipError_t launch_nmpc_after(int batch, int it, const int* conv, int* done, int*
 
 hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, int mode,
                                  const double* xs, const double* us,
-                                 const srbd_qp_data_f64& out, hipStream_t stream) {
+                                 const srbd_qp_data_f64& out, hipStream_t stream,
+                                 const srbd_plan_f64* plan) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
-  LinArgs a{batch, N, mode, xs, us, out, p.qf_scale};
+  const LinArgs a{batch, N, mode, xs, us, out, p.qf_scale};
   // S = 0 (the SRBD cost has no cross term); C = 0 only when the caller asks for it
   hipError_t e = hipMemsetAsync(const_cast<double*>(out.S), 0, sizeof(double) * 144 * (size_t)batch * N, stream);
   if (e == hipSuccess && mode == 2 && out.C)
     e = hipMemsetAsync(const_cast<double*>(out.C), 0, sizeof(double) * 288 * (size_t)batch * (N + 1), stream);
   if (e != hipSuccess) return e;
   const long long nst = (long long)batch * N;
-  hipLaunchKernelGGL(srbd_lin_stage_kernel, dim3((unsigned)((nst + kLinThreads - 1) / kLinThreads)),
-                     dim3(kLinThreads), 0, stream, m, a);
   const long long ncost = (long long)batch * (N + 1) * (72 + 12) + (mode == 2 ? (long long)batch * 24 : 0);
-  hipLaunchKernelGGL(srbd_lin_cost_kernel, dim3((unsigned)((ncost + 255) / 256)), dim3(256), 0, stream, m, a);
+  const dim3 gstage((unsigned)((nst + kLinThreads - 1) / kLinThreads)), gcost((unsigned)((ncost + 255) / 256));
+  if (plan_given(plan)) {
+    LinArgsT<true> ap;
+    static_cast<LinArgs&>(ap) = a;
+    static_cast<srbd_plan_f64&>(ap) = *plan;
+    hipLaunchKernelGGL(srbd_lin_stage_kernel<true>, gstage, dim3(kLinThreads), 0, stream, m, ap);
+    hipLaunchKernelGGL(srbd_lin_cost_kernel<true>, gcost, dim3(256), 0, stream, m, ap);
+  } else {
+    LinArgsT<false> an;
+    static_cast<LinArgs&>(an) = a;
+    hipLaunchKernelGGL(srbd_lin_stage_kernel<false>, gstage, dim3(kLinThreads), 0, stream, m, an);
+    hipLaunchKernelGGL(srbd_lin_cost_kernel<false>, gcost, dim3(256), 0, stream, m, an);
+  }
   return hipGetLastError();
 }
 

@@ -1327,9 +1327,10 @@ void srbd_qp_srbd_default_params(srbd_model_params* p) {
   p->qf_scale = 0.0;  // N
 }
 
-int srbd_qp_srbd_linearize_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
-                               int constraints, const double* xs, const double* us,
-                               const srbd_qp_data_f64* out, void* stream) {
+// The _plan_ entry points hold the checks and the work; the plain ones forward a NULL plan.
+int srbd_qp_srbd_linearize_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                    const srbd_plan_f64* plan, int constraints, const double* xs,
+                                    const double* us, const srbd_qp_data_f64* out, void* stream) {
   if (!h || !params || !xs || !us || !out) return fail(SRBD_QP_EINVAL, "NULL argument");
   const srbd_qp_dims& d = h->dims;
   if (d.nx != 12 || d.nu != 12) return fail(SRBD_QP_EDIM, "SRBD linearisation needs nx = nu = 12");
@@ -1347,9 +1348,14 @@ int srbd_qp_srbd_linearize_f64(srbd_qp_handle h, int batch, const srbd_model_par
   if (p.qf_scale <= 0.0) p.qf_scale = (double)d.N;
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
   srbd::DeviceGuard guard(h->device);
-  const hipError_t e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, *out, strm);
+  const hipError_t e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, *out, strm, plan);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
+}
+int srbd_qp_srbd_linearize_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                               int constraints, const double* xs, const double* us,
+                               const srbd_qp_data_f64* out, void* stream) {
+  return srbd_qp_srbd_linearize_plan_f64(h, batch, params, nullptr, constraints, xs, us, out, stream);
 }
 
 void srbd_qp_srbd_default_linesearch(srbd_linesearch_params* p) {
@@ -1363,10 +1369,10 @@ void srbd_qp_srbd_default_linesearch(srbd_linesearch_params* p) {
   p->alpha_min = 1e-4;
 }
 
-int srbd_qp_srbd_linesearch_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
-                                const srbd_linesearch_params* ls, double* xs, double* us,
-                                const double* dx, const double* du, double* alpha, double* merit,
-                                int* converged, void* stream) {
+int srbd_qp_srbd_linesearch_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                     const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                                     double* xs, double* us, const double* dx, const double* du,
+                                     double* alpha, double* merit, int* converged, void* stream) {
   if (!h || !params || !ls || !xs || !us || !dx || !du || !alpha)
     return fail(SRBD_QP_EINVAL, "NULL argument");
   const srbd_qp_dims& d = h->dims;
@@ -1379,15 +1385,23 @@ int srbd_qp_srbd_linesearch_f64(srbd_qp_handle h, int batch, const srbd_model_pa
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
   srbd::DeviceGuard guard(h->device);
   const hipError_t e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, dx, du, alpha,
-                                                    merit, converged, strm);
+                                                    merit, converged, strm, nullptr, plan);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
+int srbd_qp_srbd_linesearch_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                const srbd_linesearch_params* ls, double* xs, double* us,
+                                const double* dx, const double* du, double* alpha, double* merit,
+                                int* converged, void* stream) {
+  return srbd_qp_srbd_linesearch_plan_f64(h, batch, params, nullptr, ls, xs, us, dx, du, alpha, merit,
+                                          converged, stream);
+}
 
-int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
-                          const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
-                          int constraints, int sqp_max_loop, double* xs, double* us,
-                          const double* x0, double* alpha, int* sqp_iter, int* converged) {
+int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                               const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                               const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                               double* xs, double* us, const double* x0, double* alpha,
+                               int* sqp_iter, int* converged) {
   if (!h || !params || !ls || !settings || !xs || !us || !x0 || !alpha || !sqp_iter || !converged)
     return fail(SRBD_QP_EINVAL, "NULL argument");
   const srbd_qp_dims& d = h->dims;
@@ -1442,14 +1456,14 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
   if (p.qf_scale <= 0.0) p.qf_scale = (double)d.N;
   // NMPC_solver.cpp:362-372: prepareQpStructures; solveQpProblems; if (checkConvergence()) break;
   for (int it = 0; it < sqp_max_loop && e == hipSuccess; ++it) {
-    e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, qd, strm);
+    e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, qd, strm, plan);
     if (e == hipSuccess)
       e = srbd::launch_nmpc_prep(batch, d.N, it, xs, x0, at(bx0), done, sqp_iter, converged, strm);
     if (e != hipSuccess) break;
     rc = solve_impl<double>(h, batch, settings, &qd, &sol, strm);
     if (rc) return rc;
     e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, at(bx), at(bu), alpha, nullptr,
-                                     conv, strm, done);
+                                     conv, strm, done, plan);
     if (e == hipSuccess)
       e = srbd::launch_nmpc_after(batch, it, conv, done, sqp_iter, converged, active, strm);
     if (e == hipSuccess)
@@ -1460,6 +1474,13 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
   if (e == hipSuccess) e = hipStreamSynchronize(strm);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("NMPC loop: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
+}
+int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                          const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
+                          int constraints, int sqp_max_loop, double* xs, double* us,
+                          const double* x0, double* alpha, int* sqp_iter, int* converged) {
+  return srbd_qp_srbd_nmpc_plan_f64(h, batch, params, nullptr, ls, settings, constraints, sqp_max_loop,
+                                    xs, us, x0, alpha, sqp_iter, converged);
 }
 
 int srbd_qp_solve_f32(srbd_qp_handle h, int batch, const srbd_qp_settings* st,

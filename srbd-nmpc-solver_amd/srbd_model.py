@@ -29,7 +29,7 @@ import numpy as np
 
 from .qp import OcpQpBatch
 
-__all__ = ["SrbdParams", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier"]
+__all__ = ["SrbdParams", "SrbdPlan", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier"]
 
 
 @dataclass(frozen=True)
@@ -54,6 +54,45 @@ class SrbdParams:
     fmin: float = 0.0
     # NMPC_solver.cpp:344-345
     x_ref: Tuple[float, ...] = (0, 0, 0.2, 0, 0, 0, 0.5, 0, 1.0, 0, 0, 0)
+
+
+@dataclass(frozen=True)
+class SrbdPlan:
+    """Per-robot, per-stage overrides of SrbdParams (the C-ABI's srbd_plan_f64): numpy
+    arrays, each optional (None: SrbdParams' value on every stage).
+
+    x_ref  [B][N+1][12]  reference state per stage (NMPCSolver::x_ref_, 12 x (N+1))
+    foot_r [B][N][3]     right-foot position at stage k
+    foot_l [B][N][3]     left-foot position
+    fz_max [B][N][2]     normal-force limit (right, left): the contact schedule"""
+    x_ref: Optional[np.ndarray] = None
+    foot_r: Optional[np.ndarray] = None
+    foot_l: Optional[np.ndarray] = None
+    fz_max: Optional[np.ndarray] = None
+
+    def robot(self, i: int) -> "SrbdPlan":
+        """Robot i's rows (the arrays without the batch dimension)."""
+        return SrbdPlan(*[None if a is None else a[i]
+                          for a in (self.x_ref, self.foot_r, self.foot_l, self.fz_max)])
+
+
+def plan_feet(p: "SrbdParams", plan: Optional[SrbdPlan]):
+    """(foot_r, foot_l) per stage, or SrbdParams' constants."""
+    pf0 = np.array(p.foot_r) if plan is None or plan.foot_r is None else np.asarray(plan.foot_r)
+    pf1 = np.array(p.foot_l) if plan is None or plan.foot_l is None else np.asarray(plan.foot_l)
+    return pf0, pf1
+
+
+def plan_cone_offsets(bc, plan: Optional[SrbdPlan]):
+    """The cone rows' constant term with the plan's force limits: row 4 of each foot
+    (fz <= fmax) takes fz_max of that foot and stage.  [..., 24] with a plan, bc without."""
+    if plan is None or plan.fz_max is None:
+        return bc
+    fz = np.asarray(plan.fz_max)
+    out = np.broadcast_to(bc, fz.shape[:-1] + (24,)).copy()
+    out[..., 4] = fz[..., 0]
+    out[..., 16] = fz[..., 1]
+    return out
 
 
 def load_mpc_option(source) -> Tuple["SrbdParams", Dict]:
@@ -151,8 +190,9 @@ def _consts(p: SrbdParams):
     return Lb, pf0, pf1
 
 
-def continuous(x, u, p: SrbdParams, jac: bool):
-    Lb, pf0, pf1 = _consts(p)
+def continuous(x, u, p: SrbdParams, jac: bool, plan: Optional[SrbdPlan] = None):
+    Lb, _, _ = _consts(p)
+    pf0, pf1 = plan_feet(p, plan)
     r, l, pos, v = x[..., 0:3], x[..., 3:6], x[..., 6:9], x[..., 9:12]
     R = expm(r)
     Jlt = jlt(r)
@@ -185,13 +225,14 @@ def continuous(x, u, p: SrbdParams, jac: bool):
     return dx, jfx, jfu
 
 
-def shooting_dynamics(x, x_next, u, p: SrbdParams):
-    """A = I + dt jfx, B = dt jfu (Euler Jacobians, :179-181), b = RK4(x,u) - x_next."""
+def shooting_dynamics(x, x_next, u, p: SrbdParams, plan: Optional[SrbdPlan] = None):
+    """A = I + dt jfx, B = dt jfu (Euler Jacobians, :179-181), b = RK4(x,u) - x_next.
+    plan: its feet (one row per stage of x) replace SrbdParams'."""
     dt = p.dt
-    k1, jfx, jfu = continuous(x, u, p, True)
-    k2, _, _ = continuous(x + 0.5 * dt * k1, u, p, False)
-    k3, _, _ = continuous(x + 0.5 * dt * k2, u, p, False)
-    k4, _, _ = continuous(x + dt * k3, u, p, False)
+    k1, jfx, jfu = continuous(x, u, p, True, plan)
+    k2, _, _ = continuous(x + 0.5 * dt * k1, u, p, False, plan)
+    k3, _, _ = continuous(x + 0.5 * dt * k2, u, p, False, plan)
+    k4, _, _ = continuous(x + dt * k3, u, p, False, plan)
     x_get = x + (dt / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
     A = np.eye(12) + dt * jfx
     B = dt * jfu
@@ -265,25 +306,31 @@ def sample_trajectories(batch, N, seed, p: SrbdParams, first: int = 0):
     return xs, us, x0
 
 
-def build_qp(xs, us, p: Optional[SrbdParams] = None, constraints: str = "none", meta=None):
+def build_qp(xs, us, p: Optional[SrbdParams] = None, constraints: str = "none", meta=None,
+             plan: Optional[SrbdPlan] = None):
     """QP data of NMPCSolver::prepareQpStructures (NMPC_solver.cpp:276-314) at the
-    linearisation points xs [B][N+1][12], us [B][N][12].  Returns (OcpQpBatch, fc)."""
+    linearisation points xs [B][N+1][12], us [B][N][12].  plan (SrbdPlan): per-robot,
+    per-stage reference, feet and force limits in place of SrbdParams' constants.
+    Returns (OcpQpBatch, fc)."""
     p = p or SrbdParams()
     batch, N = us.shape[0], us.shape[1]
-    A, B, b = shooting_dynamics(xs[:, :-1], xs[:, 1:], us, p)
+    A, B, b = shooting_dynamics(xs[:, :-1], xs[:, 1:], us, p, plan)
     Ac, bc = friction_cone(p)
-    fc = np.einsum("ij,bkj->bki", Ac, us) + bc
+    fc = np.einsum("ij,bkj->bki", Ac, us) + plan_cone_offsets(bc, plan)
     _, db, ddb = barrier(fc, p.mu_b, p.theta_b)
     Qd = np.diag(np.array(p.Q, dtype=np.float64))
     Qf = float(N) * np.diag(np.array(p.Qf, dtype=np.float64))  # Qf_ = N * Qf (NMPC_solver.cpp:58)
     Rm = p.R * np.eye(12)
     xr = np.array(p.x_ref, dtype=np.float64)
+    xr_k, xr_N = xr, xr
+    if plan is not None and plan.x_ref is not None:
+        xr_k, xr_N = np.asarray(plan.x_ref)[:, :N], np.asarray(plan.x_ref)[:, N]
     Q = np.empty((batch, N + 1, 12, 12))
     Q[:, :N] = Qd
     Q[:, N] = Qf
     q = np.empty((batch, N + 1, 12))
-    q[:, :N] = np.einsum("ij,bkj->bki", Qd, xs[:, :N] - xr)
-    q[:, N] = np.einsum("ij,bj->bi", Qf, xs[:, N] - xr)
+    q[:, :N] = np.einsum("ij,bkj->bki", Qd, xs[:, :N] - xr_k)
+    q[:, N] = np.einsum("ij,bj->bi", Qf, xs[:, N] - xr_N)
     R = Rm + np.einsum("ci,bkc,cj->bkij", Ac, ddb, Ac)
     r = np.einsum("ij,bkj->bki", Rm, us) + np.einsum("ci,bkc->bki", Ac, db)
     S = np.zeros((batch, N, 12, 12))
@@ -291,7 +338,12 @@ def build_qp(xs, us, p: Optional[SrbdParams] = None, constraints: str = "none", 
                     meta=dict(meta or {}, constraints=constraints))
     if constraints == "box_u":
         qp.lbu = U_BOX_LO - us
-        qp.ubu = U_BOX_HI - us
+        hi = U_BOX_HI
+        if plan is not None and plan.fz_max is not None:  # the schedule caps each foot's fz
+            hi = np.broadcast_to(U_BOX_HI, us.shape).copy()
+            hi[..., 2] = np.minimum(hi[..., 2], plan.fz_max[..., 0])
+            hi[..., 8] = np.minimum(hi[..., 8], plan.fz_max[..., 1])
+        qp.ubu = hi - us
     elif constraints == "cone":
         qp.ng = 24
         qp.D = np.broadcast_to(Ac, (batch, N, 24, 12)).copy()

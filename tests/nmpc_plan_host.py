@@ -1,0 +1,115 @@
+"""TEST INFRASTRUCTURE ONLY -- the host restatement of the filter line search and of the SQP
+loop (oracle/nmpc_linesearch.py) with a plan: a per-stage reference x_ref[k], per-stage feet
+and per-stage, per-foot force limits fz_max[k] (srbd_model.SrbdPlan, one robot's rows).
+
+With a plan that repeats SrbdParams' constants every function here performs the operations of
+its twin in oracle/nmpc_linesearch.py in the same order, so the results are the same bits
+(tests/test_plan_cpu.py holds it to that).
+
+`line_search` also returns the smallest relative margin |a - b| / max(|a|, |b|) over every
+comparison between computed quantities that it evaluated (the filter's accept / reject tests
+and the convergence test).  A device run may differ from the host in the last bits of phi and
+theta; it takes the same decisions whenever that margin is far above those bits."""
+from __future__ import annotations
+
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "oracle"))
+from nmpc_linesearch import LS_DEFAULTS, _barrier_value  # noqa: E402
+
+__all__ = ["LS_DEFAULTS", "merit", "line_search", "sqp_loop"]
+
+
+def merit(srbd_model, p, plan, xs, us, N, Ac, bc):
+    """(phi, theta, Jphi_x, Jphi_u) of one robot's trajectory under its plan."""
+    Qd = np.array(p.Q, dtype=np.float64)
+    Qf = float(N) * np.array(p.Qf, dtype=np.float64)
+    xr = np.array(p.x_ref, dtype=np.float64)
+    xr = np.broadcast_to(xr, (N + 1, 12)) if plan is None or plan.x_ref is None else plan.x_ref
+    bck = np.broadcast_to(srbd_model.plan_cone_offsets(bc, plan), (N, 24))
+    phi = 0.0
+    theta = 0.0
+    Jx = np.zeros((N + 1, 12))
+    Ju = np.zeros((N, 12))
+    _, _, b = srbd_model.shooting_dynamics(xs[:N], xs[1:], us, p, plan)  # b = -f per stage
+    for k in range(N + 1):
+        e = xs[k] - xr[k]
+        if k == N:
+            phi += 0.5 * e @ (Qf * e)
+            Jx[k] = Qf * e
+            continue
+        f = -b[k]
+        theta += 0.5 * f @ f
+        phi += 0.5 * e @ (Qd * e)
+        Jx[k] = Qd * e
+        fc = Ac @ us[k] + bck[k]
+        bsum, db = 0.0, np.zeros(24)
+        for c in range(24):
+            bv, db[c] = _barrier_value(fc[c], p.mu_b, p.theta_b)
+            bsum += bv
+        phi += bsum + 0.5 * p.R * (us[k] @ us[k])
+        Ju[k] = Ac.T @ db + p.R * us[k]
+    return phi, theta, Jx, Ju
+
+
+class _Margin:
+    """Runs the comparisons and remembers the tightest one."""
+
+    def __init__(self):
+        self.smallest = np.inf
+
+    def lt(self, a, b):
+        scale = max(abs(a), abs(b))
+        self.smallest = min(self.smallest, abs(a - b) / scale if scale > 0.0 else np.inf)
+        return a < b
+
+
+def line_search(srbd_model, p, plan, xs, us, dx, du, alpha, ls=None):
+    """One robot.  Returns (xs_new, us_new, alpha_new, phi, theta, dphi, converged, margin)."""
+    ls = dict(LS_DEFAULTS, **(ls or {}))
+    N = us.shape[0]
+    Ac, bc = srbd_model.friction_cone(p)
+    phi, theta, Jx, Ju = merit(srbd_model, p, plan, xs, us, N, Ac, bc)
+    dphi = float(np.sum(dx * Jx) + np.sum(du * Ju))
+    m = _Margin()
+    xs_new, us_new = xs, us
+    while alpha > ls["alpha_min"]:
+        xa = xs + alpha * dx
+        ua = us + alpha * du
+        phi_a, theta_a, _, _ = merit(srbd_model, p, plan, xa, ua, N, Ac, bc)
+        if m.lt(ls["theta_max"], theta_a):
+            if m.lt(theta_a, (1.0 - ls["beta_theta"]) * theta):
+                xs_new, us_new = xa, ua
+                break
+        elif m.lt(max(theta_a, theta), ls["theta_min"]) and m.lt(dphi, 0.0):
+            if m.lt(phi_a, phi + ls["eta"] * alpha * dphi):
+                xs_new, us_new = xa, ua
+                break
+        else:
+            if m.lt(phi_a, phi - ls["beta_phi"] * theta) or m.lt(theta_a, (1.0 - ls["beta_theta"]) * theta):
+                xs_new, us_new = xa, ua
+                break
+        alpha = ls["beta_alpha"] * alpha
+    converged = m.lt(-1e-3, dphi) and m.lt(theta, 1e-6)
+    return xs_new, us_new, alpha, phi, theta, dphi, converged, m.smallest
+
+
+def sqp_loop(srbd_model, oracle, p, plan, xs, us, x0, alpha, settings, sqp_max_loop, constraints="none"):
+    """One robot through the SQP loop under its plan (rows without the batch dimension).
+    Returns (xs, us, alpha, sqp_iterations, converged, smallest margin of all line searches)."""
+    xs, us = xs.copy(), us.copy()
+    batched = None if plan is None else srbd_model.SrbdPlan(
+        *[None if a is None else a[None] for a in (plan.x_ref, plan.foot_r, plan.foot_l, plan.fz_max)])
+    it, conv, margin = 0, False, np.inf
+    for it in range(1, sqp_max_loop + 1):
+        qp, _ = srbd_model.build_qp(xs[None], us[None], p, constraints, plan=batched)
+        sol = oracle.solve(qp, settings, x0=(x0 - xs[0])[None])
+        xs, us, alpha, _, _, _, conv, mg = line_search(srbd_model, p, plan, xs, us, sol["x"][0],
+                                                       sol["u"][0], alpha)
+        margin = min(margin, mg)
+        if conv:
+            break
+    return xs, us, alpha, it, conv, margin
