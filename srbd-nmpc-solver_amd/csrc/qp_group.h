@@ -394,8 +394,9 @@ __device__ __forceinline__ void store_packed_col(T* pk, int lane, const T (&v)[1
 // for every r, c in 0..11, and select: a load under a lane-dependent condition becomes a
 // branch of its own that waits for its load, one memory round trip per element.)
 // row r (= column r) of a symmetric matrix stored as its packed lower triangle
-template <typename T>
-__device__ __forceinline__ void load_packed_sym(const T* pk, int r, T (&v)[12]) {
+// (Ptr: a pointer to T in any address space)
+template <typename Ptr, typename T>
+__device__ __forceinline__ void load_packed_sym(Ptr pk, int r, T (&v)[12]) {
   const int cr = packed_col(r) - r;
   sfor<0, 12>([&](auto j) {
     constexpr int J = decltype(j)::value;

@@ -12,7 +12,11 @@
 //   forward  k = 0..N   : row-owned u = K x + k, pi = P x + p,
 //                         x+ = A x + B u + b, with x, u broadcast by DPP.
 // The forward sweep reads the records in LIFO order (stage 0 was written
-// last), so the most recent records are still in L2 / Infinity Cache.
+// last).  By then every record but the last two has left the caches (the
+// chip moves ~(2k + 1) x 55 MB between the write and the read of stage k's),
+// so they stream through the HBM workspace; the fp64 large-batch kernel keeps
+// the records of stages 0 and 1 in the wave's LDS image instead and never
+// sends them to the workspace (riccati_unconstr_impl.h, HbmSrc).
 //
 // The stage-0 block is factorized in full with x_0 = x0 fixed, which gives
 // exactly the values of the reference's x0-eliminated solve + stage-0

@@ -7,7 +7,9 @@
 //                                          workgroup; blocks streamed from HBM, records
 //                                          in the stage-major HBM workspace (fp64: each
 //                                          wave writes its four records through an LDS
-//                                          image as whole 16-byte pieces).
+//                                          image as whole 16-byte pieces, and the records
+//                                          of stages 0 and 1, where the sweeps turn
+//                                          round, stay in LDS and never go to HBM).
 //   riccati_unconstr_lds_kernel  (LdsSrc)  small batches (the reference's one QP per
 //                                          solve() call): one QP per workgroup; the whole
 //                                          QP is first copied into an LDS image with
@@ -46,13 +48,24 @@ struct HbmSrc {
   __device__ const real* r(int k) const { return at(a.r, a.N, 12, k); }
   __device__ real* rec(int k) const { return a.ws + ((size_t)k * a.batch + qp) * kWsStage; }
   // fp64 large-batch kernel: the wave's LDS image of its four QPs' records (null: plain
-  // stores)
+  // stores).  Two slots of four records: slot A (img) stages the records on their way to
+  // the workspace and then keeps stage 0's; slot B (img + 4 * kWsStage) keeps stage 1's.
+  // Those two are the last the backward sweep writes and the first the forward sweep
+  // reads, so they never leave the chip: their workspace slots go unused.
   real* img = nullptr;  // the wave's image base: group g's record at img + g * kWsStage
   int gq = 0;           // QP group in the wave
+  // the kept record of stage k = 0, 1 (an LDS address: never mix it with rec(k) in one
+  // pointer, which would make every load through it a flat one)
+  __device__ real* kept(int k) const { return img + (k * 4 + gq) * kWsStage; }
   // stage k's record, `store` writing it at a given base (defined after store_rec below)
   template <class StoreRec>
   __device__ void store_stage(int k, StoreRec&& store) const;
 };
+
+// the forward sweep reads stages 0 and 1 (stage N, the terminal record, excepted) from the
+// wave's image: HbmSrc in fp64, where the large-batch kernel always sets img
+template <class Src>
+constexpr bool keeps_turnaround = std::is_same_v<Src, HbmSrc> && sizeof(real) == 8;
 
 // LDS image of one QP: stage slot k (k = 0..N) holds the stage's blocks at the offsets
 // below (slot N: Q and q only); after the backward sweep has used slot k's Q, S, R, the
@@ -108,10 +121,18 @@ constexpr int kRecHotStages = 4;
 // A stage record by plain stores, or (img set) through the wave's LDS image: the four
 // groups write their records into the image, then the wave stores the four records, which
 // are contiguous in the stage-major workspace, as whole 16-byte pieces in lane order.
+// Stages 0 and 1 are only written into their slots of the image (slot A is free by then:
+// the copy-out of stage 2 ended with a fence).
 template <class StoreRec>
 __device__ void HbmSrc::store_stage(int k, StoreRec&& store) const {
   if (!img) {
     store(rec(k));
+    return;
+  }
+  if (k < 2) {  // (k == 1 is a backward stage only when N >= 2, so never the terminal one)
+    store(kept(k));
+    // the forward sweep's lanes read rows that other lanes of their group wrote
+    lds_wave_fence();
     return;
   }
   store(img + gq * kWsStage);
@@ -190,7 +211,34 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
       b_ = src.b(k)[row];
     }
   };
-  load_rows(0, Pr, Kr, Ar, pv, kv, bv);
+  // The same rows where stage k's record is the one kept in the wave's LDS image (k < N),
+  // read through a pointer typed as an LDS address.  The callers branch on where the record
+  // is (k is the same in every lane), so a kept record's loads are LDS loads and a streamed
+  // one's stay global loads; one generic pointer for both would make all of them flat loads.
+  auto load_rows_kept = [&](int k, real (&P_)[12], real (&K_)[12], real (&A__)[12], real& p_, real& k_,
+                            real& b_) {
+    if constexpr (keeps_turnaround<Src>) {
+      const auto rec = (const __attribute__((address_space(3))) real*)src.kept(k);
+      load_packed_sym(rec + kWsP, row, P_);
+      p_ = rec[kWsp + row];
+      const auto kr = rec + kWsK + row * kWsRow;
+      const real* Ab = src.A(k);
+      sfor<0, 12>([&](auto j) {
+        constexpr int J = decltype(j)::value;
+        K_[J] = kr[J];
+        A__[J] = Ab[J * 12 + row];
+      });
+      k_ = kr[12];
+      b_ = src.b(k)[row];
+    }
+  };
+  // stage k's record is kept (k = 0, 1, the terminal stage N excepted)
+  auto kept = [&](int k) { return keeps_turnaround<Src> && k < 2 && k < N; };
+  if (kept(0)) {
+    load_rows_kept(0, Pr, Kr, Ar, pv, kv, bv);
+  } else {
+    load_rows(0, Pr, Kr, Ar, pv, kv, bv);
+  }
 #pragma unroll 1
   for (int k = 0; k <= N; ++k) {
     // this stage's B row (used last: its load overlaps P x, K x, A x), then stage k+1's rows
@@ -200,7 +248,13 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
       sfor<0, 12>([&](auto j) { Br[decltype(j)::value] = Bb[decltype(j)::value * 12 + row]; });
     }
     real Pn[12], Kn[12], An[12], pvn = real(0.0), kvn = real(0.0), bvn = real(0.0);
-    if (k < N) load_rows(k + 1, Pn, Kn, An, pvn, kvn, bvn);
+    if (k < N) {
+      if (kept(k + 1)) {
+        load_rows_kept(k + 1, Pn, Kn, An, pvn, kvn, bvn);
+      } else {
+        load_rows(k + 1, Pn, Kn, An, pvn, kvn, bvn);
+      }
+    }
     real bx[12];
     sfor<0, 12>([&](auto j) {
       constexpr int J = decltype(j)::value;
@@ -331,18 +385,21 @@ __device__ __forceinline__ void solve_qp(const ProblemArgsT<real>& a, const Src&
 }
 
 // Large batches: 16 QPs per 256-thread workgroup, 2 workgroups per CU (the kernel needs
-// 217-224 VGPRs; memory-bound with the compute overlapped).  fp64: each
-// wave's stage records go out through its 12.6 KiB LDS image (HbmSrc::store_stage).
+// 254 VGPRs in fp64; memory-bound with the compute overlapped).  fp64: each
+// wave's stage records go out through slot A of its LDS image, and those of stages 0 and 1
+// stay in slots A and B for the forward sweep (HbmSrc::store_stage): 2 x 7.7 KiB a wave,
+// 61.5 KiB a workgroup, two workgroups in a CU's 160 KiB.
 template <bool SQRT>
 __global__ void __launch_bounds__(256, 2) riccati_unconstr_kernel(ProblemArgsT<real> a) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int qp = gid >> 4;
   if (qp >= a.batch) return;
   if constexpr (sizeof(real) == 8) {  // fp64 records are whole 16-byte pieces per QP
-    __shared__ __attribute__((aligned(16))) real rec_img[16 * kWsStage];
+    __shared__ __attribute__((aligned(16))) real rec_img[4 * 2 * 4 * kWsStage];
+    static_assert(sizeof(rec_img) <= 64 * 1024, "static LDS limit");
     HbmSrc src{a, qp};
     src.gq = (threadIdx.x >> 4) & 3;
-    src.img = rec_img + (threadIdx.x >> 6) * 4 * kWsStage;
+    src.img = rec_img + (threadIdx.x >> 6) * 2 * 4 * kWsStage;
     solve_qp<SQRT>(a, src, qp, threadIdx.x & (kGroup - 1));
   } else {
     solve_qp<SQRT>(a, HbmSrc{a, qp}, qp, threadIdx.x & (kGroup - 1));
