@@ -29,6 +29,9 @@
  *   srbd_qp_srbd_*_plan_f64      the same three with a srbd_plan_f64: a reference trajectory
  *                                (NMPCSolver::x_ref_), a footstep plan and a contact schedule
  *                                per robot and stage.
+ *   srbd_qp_srbd_advance_f64     what a controller does between two steps: apply u[0], move the
+ *                                plant, shift the previous solution by one stage.
+ *   srbd_qp_srbd_rollout_f64     T ticks of the closed receding-horizon loop around the step.
  *
  * ------------------------------------------------------------------------
  * Problem (per QP, stages k = 0..N), identical to hpipm::OcpQp
@@ -490,6 +493,86 @@ int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_par
                                int* sqp_iter, int* converged);
 
 /* ------------------------------------------------------------------------
+ * The closed loop (additive to ABI 12): what a controller or a batched simulation does
+ * between two NMPC steps, and T ticks of the whole receding-horizon loop.  The reference
+ * stops at one step (NMPCSolver::controlLoop repeats it N_rep times for timing); the loop
+ * every caller writes around a step is hpipm-cpp/examples/example_mpc.cpp's: apply u[0],
+ * move the plant, shift the previous solution by one stage, slide the plan's window.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_advance_f64 {
+  int substeps;          /* plant RK4 steps per tick, each dt / substeps; >= 1            */
+  const double* wrench;  /* [batch][6] external torque (3) and force (3) on the body, world
+                          * frame, held over the tick; NULL = none                         */
+} srbd_advance_f64;
+
+/* One tick's plant step and shift of the guess.  Asynchronous on `stream` (NULL = the
+ * handle's own stream); all memory is device memory, xs / us 16-byte aligned.  Per robot, in
+ * this order:
+ *  1. Applied input: u0 = us[0], written to u_applied ([batch][12]) when that is given.
+ *  2. Plant step, when x ([batch][12], in place) is given: x is replaced by `substeps`
+ *     classical RK4 steps of length dt / substeps of xdot = f(x, u0) + w.  f is the SRBD
+ *     continuous model (SRBDModel::GetContinuousDynamic) with the feet of stage 0 of
+ *     plan->foot_r / foot_l, or params->foot_* where that field or the plan is NULL; w adds
+ *     wrench[0:3] to rows 3..5 (the angular-momentum rate) and wrench[3:6] / mass to rows
+ *     9..11.  The plant applies u0 as it is: it clamps nothing and applies no fz_max.
+ *  3. New last stage: xN = one RK4 step of the model over dt from the old xs[N] with the old
+ *     us[N-1] and the feet of the plan's stage N-1, no wrench: the shifted guess has zero
+ *     shooting defect at its last stage.
+ *  4. Shift: xs[k] <- xs[k+1] for k = 0..N-1, then xs[N] <- xN; us[k] <- us[k+1] for
+ *     k = 0..N-2, us[N-1] stays.  Shifted entries are bit copies.  xs[0] is the old xs[1], not
+ *     x: the step forms x0 - xs[:, 0] itself (NMPC_solver.cpp:320).
+ * `plan` is this tick's window (may be NULL); only its feet are read.
+ * Checks: NULL h / params / adv / xs / us and substeps < 1 are SRBD_QP_EINVAL; the handle
+ * needs nx = nu = 12 (SRBD_QP_EDIM); batch above the capacity is SRBD_QP_ECAPACITY;
+ * batch == 0 returns SRBD_QP_OK.                                                    */
+int srbd_qp_srbd_advance_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                             const srbd_plan_f64* plan,   /* this tick's window, may be NULL */
+                             const srbd_advance_f64* adv,
+                             double* xs, double* us,      /* [batch][N+1][12], [batch][N][12], in place */
+                             double* x,                   /* [batch][12] plant state, in place; NULL = shift only */
+                             double* u_applied,           /* [batch][12] out, optional       */
+                             void* stream);
+
+typedef struct srbd_rollout_f64 {
+  int ticks;             /* T >= 0                                                         */
+  int plan_stages;       /* P: stages per robot in the plan's arrays (x_ref [batch][P+1][12],
+                          * foot_* [batch][P][3], fz_max [batch][P][2]); P >= N + T - 1.
+                          * Ignored when plan is NULL / all fields NULL.                    */
+  int substeps;          /* as srbd_advance_f64                                            */
+  const double* wrench;  /* [batch][T][6], NULL = none                                     */
+  double alpha_reset;    /* > 0: every tick starts its line search from this alpha;
+                          * 0: alpha persists across ticks like the reference's alpha_      */
+  double* x_log;         /* [batch][T+1][12] optional: x_log[0] = the x passed in           */
+  double* u_log;         /* [batch][T][12]   optional: the applied inputs                   */
+  int* sqp_iter_log;     /* [batch][T] optional                                             */
+  int* converged_log;    /* [batch][T] optional                                             */
+} srbd_rollout_f64;
+
+/* T ticks of the closed loop.  Synchronous (it inherits the step's per-iteration read-back),
+ * on the handle's stream.  For t = 0..T-1:
+ *  1. the window W_t = stages t..t+N of the long plan (x_ref rows t..t+N, feet and fz_max
+ *     rows t..t+N-1; NULL fields stay NULL) is gathered dense into a scratch buffer of the
+ *     handle (allocated on the first rollout with a plan, capacity-sized; counted by
+ *     srbd_qp_memory_bytes);
+ *  2. if alpha_reset > 0, every robot's alpha is set to it.  The line search leaves a
+ *     shrunken alpha behind and nothing restores it: with alpha_reset = 0 (the reference's
+ *     persistent alpha_) later ticks may start from a step length too small to converge;
+ *  3. srbd_qp_srbd_nmpc_plan_f64 runs with W_t and x0 = x;
+ *  4. its sqp_iter / converged go to column t of the logs;
+ *  5. srbd_qp_srbd_advance_f64 runs with W_t and wrench[:, t];
+ *  6. u_log[:, t] and x_log[:, t+1] are written.
+ * On return x is the plant state after T ticks, xs / us the shifted guess for tick T and alpha
+ * as the last step left it.  The results are the bits of a caller's loop over 1-6 through the
+ * two public entry points.  ticks == 0 or batch == 0 returns SRBD_QP_OK (x_log[:, 0] written
+ * when given and batch > 0); plan_stages < N + T - 1 with a non-empty plan, substeps < 1 and a
+ * negative alpha_reset are SRBD_QP_EINVAL; the other checks are the step's.            */
+int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                             const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                             const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                             const srbd_rollout_f64* roll,
+                             double* xs, double* us, double* x, double* alpha);
+
+/* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,
  * "one process, 8 devices"; BASELINE config 4: a batch sharded over 8 MI355X
  * with the solutions gathered to one device).  A handle per device; the
@@ -531,8 +614,8 @@ size_t srbd_qp_workspace_bytes(srbd_qp_handle h);
 
 /* Every byte the handle holds right now: the workspace plus the buffers it
  * allocates on first use (host-solve staging and its pinned host mirror, the
- * 12 x 12 embedding, the NMPC loop state, the f64_rescue / f32_iters
- * batches).  A pool of handles (hpipm-cpp's, which re-implements the
+ * 12 x 12 embedding, the NMPC loop state, the rollout's plan window, the
+ * f64_rescue / f32_iters batches).  A pool of handles (hpipm-cpp's, which re-implements the
  * reference's construct-per-solve pattern, NMPC_solver.cpp:318-319) sizes
  * itself by this.  (ABI 9)                                                  */
 size_t srbd_qp_memory_bytes(srbd_qp_handle h);

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""The inputs and the tolerance table of tests/test_gpu_rollout.py's comparison with the host
+closed loop, computed on the CPU.
+
+For each case (constraints, alpha_reset) of the test and a seed of rollout_host.walking_case:
+  * the conditions on the inputs: the host loop's smallest comparison margin over all ticks
+    (wanted >= 1e-6) and the SQP iteration counts (wanted: at least two distinct);
+  * d_t: the largest change of the host loop's x_log[t] / u_log[t-1] when the loop is rerun with
+    x, xs, us perturbed by relative 1e-7 (every entry times 1 +- 1e-7, random signs; the largest
+    over --draws draws).  That is the largest device-host gap the step test's tolerance
+    (rtol 1e-7) admits after one step, carried through the later ticks.
+
+    python scripts/rollout_sensitivity.py --seed 30            # the table of the test's seed
+    python scripts/rollout_sensitivity.py --search 20 40       # seeds that meet the conditions
+"""
+import argparse
+import sys
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(REPO / "tests"))
+sys.path.insert(0, str(REPO / "oracle"))
+
+import helpers  # noqa: E402
+import rollout_host as RH  # noqa: E402
+
+NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
+            tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
+            split_step=1)
+CASES = [(c, a) for c in ("none", "box_u") for a in (0.0, 1.0)]
+B, N, T = 4, 10, 4
+
+
+def run(sm, oracle, p, case, inputs):
+    xs, us, x, alpha, plan = inputs
+    return RH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, 15, case[0], alpha_reset=case[1])
+
+
+def conditions(sm, oracle, p, seed):
+    inputs = RH.walking_case(sm, p, B, N, T, seed)
+    out = {}
+    for case in CASES:
+        h = run(sm, oracle, p, case, inputs)
+        out[case] = (h["margin"], sorted(set(h["sqp_iter"].ravel().tolist())), h)
+    return inputs, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seed", type=int, default=30)
+    ap.add_argument("--search", type=int, nargs=2, metavar=("FROM", "TO"))
+    ap.add_argument("--draws", type=int, default=3)
+    a = ap.parse_args()
+    sm, oracle = helpers.load_package().srbd_model, helpers.load_oracle()
+    p = sm.SrbdParams()
+    if a.search:
+        for seed in range(a.search[0], a.search[1]):
+            _, c = conditions(sm, oracle, p, seed)
+            ok = all(m >= 1e-6 and len(its) >= 2 for m, its, _ in c.values())
+            print(seed, "OK " if ok else "-- ", {k: (f"{m:.1e}", its) for k, (m, its, _) in c.items()}, flush=True)
+        return
+    inputs, c = conditions(sm, oracle, p, a.seed)
+    xs, us, x, alpha, plan = inputs
+    for case in CASES:
+        margin, its, base = c[case]
+        print(f"{case}: margin {margin:.2e}, sqp iterations {its}\n{base['sqp_iter']}")
+        dx, du = np.zeros(T), np.zeros(T)
+        for d in range(a.draws):
+            rng = np.random.default_rng([a.seed, d])
+            pert = lambda v: v * (1.0 + 1e-7 * rng.choice([-1.0, 1.0], size=v.shape))
+            h = run(sm, oracle, p, case, (pert(xs), pert(us), pert(x), alpha, plan))
+            same = np.array_equal(h["sqp_iter"], base["sqp_iter"])
+            dx = np.maximum(dx, np.abs(h["x_log"][:, 1:] - base["x_log"][:, 1:]).max(axis=(0, 2)))
+            du = np.maximum(du, np.abs(h["u_log"] - base["u_log"]).max(axis=(0, 2)))
+            print(f"  draw {d}: same iteration counts {same}")
+        fmt = lambda v: "(" + ", ".join(f"{e:.1e}" for e in v) + ")"
+        print(f"    {case!r}: ({fmt(dx)}, {fmt(du)}),")
+
+
+if __name__ == "__main__":
+    main()

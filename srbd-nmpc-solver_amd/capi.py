@@ -129,7 +129,8 @@ class Plan:
         self.x_ref, self.foot_r, self.foot_l, self.fz_max = x_ref, foot_r, foot_l, fz_max
 
     def struct(self, B: int, N: int, device=None) -> PlanStruct:
-        """The C struct for a batch of B robots over N stages; ValueError on a mismatch."""
+        """The C struct for a batch of B robots over N stages (the horizon, or the P stages of a
+        rollout's long plan); ValueError on a mismatch."""
         import torch
         ps = PlanStruct()
         for name, (extra, width) in self.FIELDS.items():
@@ -152,6 +153,18 @@ class Plan:
 def _plan_ref(plan: Optional["Plan"], B: int, N: int, device):
     """byref(PlanStruct) or None (a NULL plan) for the _plan_ entry points."""
     return None if plan is None else C.byref(plan.struct(B, N, device))
+
+
+class AdvanceStruct(C.Structure):
+    """srbd_advance_f64."""
+    _fields_ = [("substeps", C.c_int), ("wrench", _dp)]
+
+
+class RolloutStruct(C.Structure):
+    """srbd_rollout_f64."""
+    _fields_ = [("ticks", C.c_int), ("plan_stages", C.c_int), ("substeps", C.c_int), ("wrench", _dp),
+                ("alpha_reset", C.c_double), ("x_log", _dp), ("u_log", _dp), ("sqp_iter_log", _dp),
+                ("converged_log", _dp)]
 
 
 _lib = None
@@ -270,6 +283,16 @@ def lib():
                                                      C.POINTER(Settings), C.c_int,
                                                      C.c_int] + [C.c_void_p] * 6
             L.srbd_qp_srbd_nmpc_plan_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_srbd_rollout_f64"):  # the closed loop (older builds: A/B runs)
+            L.srbd_qp_srbd_advance_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                   C.POINTER(PlanStruct),
+                                                   C.POINTER(AdvanceStruct)] + [C.c_void_p] * 5
+            L.srbd_qp_srbd_advance_f64.restype = C.c_int
+            L.srbd_qp_srbd_rollout_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                   C.POINTER(PlanStruct), C.POINTER(LsParams),
+                                                   C.POINTER(Settings), C.c_int, C.c_int,
+                                                   C.POINTER(RolloutStruct)] + [C.c_void_p] * 4
+            L.srbd_qp_srbd_rollout_f64.restype = C.c_int
         L.srbd_qp_abi_version.argtypes = []
         L.srbd_qp_abi_version.restype = C.c_int
         _lib = L
@@ -681,3 +704,91 @@ def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
               "srbd_qp_srbd_nmpc_plan_f64")
     _order_after(o)
     return it, conv
+
+
+def _check_f64(name, t, shape, device):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+        raise ValueError(f"{name} must be a torch.float64 tensor")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the trajectories on {device}")
+
+
+def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wrench=None,
+                 substeps: int = 1, params: Optional[ModelParams] = None, stream: int = 0):
+    """One control tick between two NMPC steps (srbd_qp_srbd_advance_f64): the applied input
+    u0 = us[:, 0]; the plant state x [B][12] (in place; None: shift only) moved by `substeps` RK4
+    steps of dt / substeps with u0, stage 0's feet of `plan` (this tick's window) and the
+    external wrench [B][6] (torque, force; None: none); xs [B][N+1][12], us [B][N][12] shifted
+    by one stage in place, the new last stage one model step from the old one.  Asynchronous on
+    the handle's stream, ordered like a torch op.  Returns u0 [B][12] (a device tensor)."""
+    import torch
+    B, N = us.shape[0], us.shape[1]
+    dev = xs.device
+    _check_f64("xs", xs, (B, N + 1, 12), dev)
+    _check_f64("us", us, (B, N, 12), dev)
+    if x is not None:
+        _check_f64("x", x, (B, 12), dev)
+    if wrench is not None:
+        _check_f64("wrench", wrench, (B, 6), dev)
+    plan_ref = _plan_ref(plan, B, N, dev)
+    u0 = torch.empty(B, 12, dtype=torch.float64, device=dev)
+    adv = AdvanceStruct(int(substeps), _tensor_ptr(wrench) or None)
+    p = params or default_model_params()
+    ptr = lambda t: C.c_void_p(_tensor_ptr(t) or None)
+    o = _order_before(handle, stream, True)
+    check(lib().srbd_qp_srbd_advance_f64(handle.ptr, int(B), C.byref(p), plan_ref, C.byref(adv), ptr(xs),
+                                         ptr(us), ptr(x), ptr(u0), C.c_void_p(stream or None)),
+          "srbd_qp_srbd_advance_f64")
+    _order_after(o)
+    return u0
+
+
+def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str = "none",
+                 settings: Optional[Dict] = None, sqp_max_loop: int = 15, plan: Optional[Plan] = None,
+                 plan_stages: Optional[int] = None, wrench=None, substeps: int = 1,
+                 alpha_reset: float = 0.0, params: Optional[ModelParams] = None,
+                 ls: Optional[LsParams] = None):
+    """`ticks` ticks of the closed receding-horizon loop on the device
+    (srbd_qp_srbd_rollout_f64): per tick the NMPC step (srbd_nmpc) from the plant state x with
+    the plan's window of that tick, then srbd_advance with wrench[:, t].  xs [B][N+1][12],
+    us [B][N][12], x [B][12], alpha [B]: torch fp64 device tensors, updated in place.
+    `plan`: a Plan over plan_stages = P >= N + ticks - 1 stages (x_ref [B][P+1][12], feet
+    [B][P][3], fz_max [B][P][2]); plan_stages defaults to N + ticks - 1.  wrench [B][ticks][6].
+    alpha_reset > 0 starts every tick's line search from that alpha; 0 keeps the reference's
+    persistent alpha_.  Synchronous.  Returns (x_log [B][ticks+1][12], u_log [B][ticks][12],
+    sqp_iter_log [B][ticks], converged_log [B][ticks]) device tensors."""
+    import torch
+    B, N, T = us.shape[0], us.shape[1], int(ticks)
+    dev = xs.device
+    _check_f64("xs", xs, (B, N + 1, 12), dev)
+    _check_f64("us", us, (B, N, 12), dev)
+    _check_f64("x", x, (B, 12), dev)
+    _check_f64("alpha", alpha, (B,), dev)
+    if wrench is not None:
+        _check_f64("wrench", wrench, (B, max(T, 0), 6), dev)
+    P = N + T - 1 if plan_stages is None else int(plan_stages)
+    plan_ref = _plan_ref(plan, B, P, dev)
+    rows = max(T, 0)
+    x_log = torch.zeros(B, rows + 1, 12, dtype=torch.float64, device=dev)
+    u_log = torch.zeros(B, rows, 12, dtype=torch.float64, device=dev)
+    it_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
+    cv_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
+    roll = RolloutStruct(T, P, int(substeps), _tensor_ptr(wrench) or None, float(alpha_reset),
+                         x_log.data_ptr(), u_log.data_ptr() or None, it_log.data_ptr() or None,
+                         cv_log.data_ptr() or None)
+    p = params or default_model_params()
+    lp = ls or default_linesearch()
+    s = settings_struct(settings)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    o = _order_before(handle, 0, True)
+    check(lib().srbd_qp_srbd_rollout_f64(handle.ptr, int(B), C.byref(p), plan_ref, C.byref(lp), C.byref(s),
+                                         SRBD_CONSTRAINTS[constraints], int(sqp_max_loop), C.byref(roll),
+                                         ptr(xs), ptr(us), ptr(x), ptr(alpha)),
+          "srbd_qp_srbd_rollout_f64")
+    _order_after(o)
+    return x_log, u_log, it_log, cv_log

@@ -244,6 +244,36 @@ hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, i
                                  const srbd_qp_data_f64& out, hipStream_t stream,
                                  const srbd_plan_f64* plan = nullptr);
 
+// srbd_rollout.hip: one tick's plant step and shift of the guess (srbd_qp_srbd_advance_f64).
+// The per-robot outputs carry a stride (doubles / ints per robot), so that the rollout writes
+// column t of its logs from the same launch.
+struct AdvanceIo {
+  int substeps;
+  double *xs, *us;       // shifted in place
+  double* x;             // plant state, in place (NULL: shift only)
+  const double* wrench;  // robot r's six values at wrench + r * wrench_stride (NULL: none)
+  long long wrench_stride;
+  double* u_out;  // the applied input, at u_out + r * u_stride (NULL: not written)
+  long long u_stride;
+  double* x_out;  // a copy of the new plant state, at x_out + r * x_stride (NULL: not written)
+  long long x_stride;
+  const int *it_src, *cv_src;  // it_log[r * log_stride] = it_src[r], cv alike (NULL logs: none)
+  int *it_log, *cv_log;
+  long long log_stride;
+};
+hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, const AdvanceIo& io,
+                               const srbd_plan_f64* plan, hipStream_t stream);
+// Up to four strided row copies, dst[r * dstride + e] = src[r * sstride + e] (e < width,
+// r < batch), and alpha[r] = alpha_value when alpha is given, in one launch.
+struct RolloutRow {
+  const double* src;
+  double* dst;
+  int width;
+  long long sstride, dstride;
+};
+hipError_t launch_rollout_rows(int batch, const RolloutRow* rows, int nrows, double* alpha,
+                               double alpha_value, hipStream_t stream);
+
 // rescue.hip (srbd_qp_settings.f64_rescue / f32_iters): list the QPs with status >=
 // min_status in batch order, widen / narrow QP-major rows of `elems` values between fp32 and fp64
 hipError_t launch_select_unsolved(const int* status, int batch, int min_status, int* idx, int* count,

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <chrono>
 #include <cstdlib>
@@ -94,6 +95,9 @@ struct srbd_qp_handle_s {
   srbd::Buffer soft_ws, soft_pad;
   // srbd_qp_srbd_nmpc_f64: QP data, solution and loop state
   srbd::Buffer nmpc;
+  // srbd_qp_srbd_rollout_f64: the step's sqp_iter / converged (capacity ints each), and the
+  // dense plan window of one tick (first rollout with a plan)
+  srbd::Buffer roll, roll_plan;
   // settings.f64_rescue: the compact fp64 batch, and that of the cold fp64 re-solve of
   // rescued QPs the continuation left unsolved
   srbd::Buffer resc, resc2;
@@ -103,7 +107,8 @@ struct srbd_qp_handle_s {
   srbd::Buffer lqsw;
   template <typename F>
   void each_buffer(F&& f) {
-    for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &resc, &resc2, &mixed, &lqsw})
+    for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &roll, &roll_plan, &resc, &resc2, &mixed,
+                            &lqsw})
       f(*b);
   }
   int* nmpc_active_host = nullptr;  // pinned
@@ -1481,6 +1486,161 @@ int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* 
                           const double* x0, double* alpha, int* sqp_iter, int* converged) {
   return srbd_qp_srbd_nmpc_plan_f64(h, batch, params, nullptr, ls, settings, constraints, sqp_max_loop,
                                     xs, us, x0, alpha, sqp_iter, converged);
+}
+
+// ---- the closed loop ----
+namespace {
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+}  // namespace
+
+int srbd_qp_srbd_advance_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                             const srbd_plan_f64* plan, const srbd_advance_f64* adv, double* xs,
+                             double* us, double* x, double* u_applied, void* stream) {
+  if (!h || !params || !adv || !xs || !us) return fail(SRBD_QP_EINVAL, "NULL argument");
+  if (adv->substeps < 1) return fail(SRBD_QP_EINVAL, "advance: substeps must be at least 1");
+  const srbd_qp_dims& d = h->dims;
+  if (d.nx != 12 || d.nu != 12) return fail(SRBD_QP_EDIM, "the SRBD plant step needs nx = nu = 12");
+  if (batch < 0 || batch > h->capacity) return fail(SRBD_QP_ECAPACITY, "batch exceeds capacity");
+  if (!aligned16(xs) || !aligned16(us)) return fail(SRBD_QP_EINVAL, "advance: xs / us must be 16-byte aligned");
+  if (batch == 0) return SRBD_QP_OK;
+  hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  srbd::DeviceGuard guard(h->device);
+  srbd::AdvanceIo io{};
+  io.substeps = adv->substeps;
+  io.xs = xs;
+  io.us = us;
+  io.x = x;
+  io.wrench = adv->wrench;
+  io.wrench_stride = 6;
+  io.u_out = u_applied;
+  io.u_stride = 12;
+  const hipError_t e = srbd::launch_srbd_advance(*params, batch, d.N, io, plan, strm);
+  if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+  return SRBD_QP_OK;
+}
+
+int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                             const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                             const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                             const srbd_rollout_f64* roll, double* xs, double* us, double* x,
+                             double* alpha) {
+  if (!h || !params || !ls || !settings || !roll || !xs || !us || !x || !alpha)
+    return fail(SRBD_QP_EINVAL, "NULL argument");
+  const srbd_qp_dims& d = h->dims;
+  if (d.nx != 12 || d.nu != 12) return fail(SRBD_QP_EDIM, "the SRBD NMPC loop needs nx = nu = 12");
+  if (batch < 0 || batch > h->capacity) return fail(SRBD_QP_ECAPACITY, "batch exceeds capacity");
+  const int T = roll->ticks, P = roll->plan_stages, N = d.N;
+  if (T < 0) return fail(SRBD_QP_EINVAL, "rollout: ticks must be non-negative");
+  if (roll->substeps < 1) return fail(SRBD_QP_EINVAL, "rollout: substeps must be at least 1");
+  if (!(roll->alpha_reset >= 0.0)) return fail(SRBD_QP_EINVAL, "rollout: alpha_reset must be non-negative");
+  const bool with_plan = plan && (plan->x_ref || plan->foot_r || plan->foot_l || plan->fz_max);
+  if (with_plan && (long long)P < (long long)N + T - 1)
+    return fail(SRBD_QP_EINVAL, "rollout: the plan needs plan_stages >= N + ticks - 1");
+  if (!aligned16(xs) || !aligned16(us)) return fail(SRBD_QP_EINVAL, "rollout: xs / us must be 16-byte aligned");
+  {  // the step's own checks (settings, constraints against the handle's dims, ...): a step of
+     // zero robots runs them and nothing else
+    int none = 0;
+    const int rc = srbd_qp_srbd_nmpc_plan_f64(h, 0, params, nullptr, ls, settings, constraints,
+                                              sqp_max_loop, xs, us, x, alpha, &none, &none);
+    if (rc) return rc;
+  }
+  if (batch == 0) return SRBD_QP_OK;
+  srbd::DeviceGuard guard(h->device);
+  hipStream_t strm = h->stream;
+  const size_t B = (size_t)h->capacity;
+  auto device_error = [&](hipError_t e, const char* what) {
+    return fail(e == hipErrorOutOfMemory ? SRBD_QP_ENOMEM : SRBD_QP_EDEVICE,
+                std::string(what) + hipGetErrorString(e));
+  };
+  hipError_t e = hipSuccess;
+  if (roll->x_log) {  // x_log[:, 0] = the x passed in
+    const srbd::RolloutRow r0{x, roll->x_log, 12, 12, (long long)(T + 1) * 12};
+    e = srbd::launch_rollout_rows(batch, &r0, 1, nullptr, 0.0, strm);
+    if (e != hipSuccess) return device_error(e, "rollout: ");
+  }
+  if (T == 0) {
+    e = hipStreamSynchronize(strm);
+    return e == hipSuccess ? SRBD_QP_OK : device_error(e, "rollout: ");
+  }
+  // scratch: the step's sqp_iter / converged, and one tick's dense plan window
+  e = h->roll.reserve(2 * B * sizeof(int));
+  const size_t wx = 12 * ((size_t)N + 1), wf = 3 * (size_t)N, wz = 2 * (size_t)N;
+  if (e == hipSuccess && with_plan) e = h->roll_plan.reserve(B * (wx + 2 * wf + wz) * sizeof(double));
+  if (e != hipSuccess) return device_error(e, "rollout scratch allocation failed: ");
+  int* it_step = h->roll.as<int>();
+  int* cv_step = it_step + B;
+  // a step that runs no SQP iteration (sqp_max_loop == 0) writes neither
+  e = hipMemsetAsync(it_step, 0, 2 * B * sizeof(int), strm);
+  if (e != hipSuccess) return device_error(e, "rollout: ");
+  srbd_plan_f64 win{};
+  srbd::RolloutRow rows[4];
+  int nrows = 0;
+  if (with_plan) {
+    double* w = h->roll_plan.as<double>();
+    double* const wxr = w;
+    double* const wfr = wxr + B * wx;
+    double* const wfl = wfr + B * wf;
+    double* const wfz = wfl + B * wf;
+    if (plan->x_ref) {
+      win.x_ref = wxr;
+      rows[nrows++] = srbd::RolloutRow{plan->x_ref, wxr, (int)wx, 12 * ((long long)P + 1), (long long)wx};
+    }
+    if (plan->foot_r) {
+      win.foot_r = wfr;
+      rows[nrows++] = srbd::RolloutRow{plan->foot_r, wfr, (int)wf, 3 * (long long)P, (long long)wf};
+    }
+    if (plan->foot_l) {
+      win.foot_l = wfl;
+      rows[nrows++] = srbd::RolloutRow{plan->foot_l, wfl, (int)wf, 3 * (long long)P, (long long)wf};
+    }
+    if (plan->fz_max) {
+      win.fz_max = wfz;
+      rows[nrows++] = srbd::RolloutRow{plan->fz_max, wfz, (int)wz, 2 * (long long)P, (long long)wz};
+    }
+  }
+  const int per_stage[4] = {12, 3, 3, 2};  // doubles per stage of x_ref, foot_r, foot_l, fz_max
+  for (int t = 0; t < T; ++t) {
+    // W_t: stages t .. t + N of the long plan, gathered dense; alpha per the reset policy
+    srbd::RolloutRow rt[4];
+    int n = 0;
+    if (with_plan) {
+      const double* fields[4] = {plan->x_ref, plan->foot_r, plan->foot_l, plan->fz_max};
+      for (int fi = 0; fi < 4; ++fi)
+        if (fields[fi]) {
+          rt[n] = rows[n];
+          rt[n].src = fields[fi] + (size_t)t * per_stage[fi];
+          ++n;
+        }
+    }
+    e = srbd::launch_rollout_rows(batch, rt, n, roll->alpha_reset > 0.0 ? alpha : nullptr,
+                                  roll->alpha_reset, strm);
+    if (e != hipSuccess) return device_error(e, "rollout: ");
+    const srbd_plan_f64* wplan = with_plan ? &win : nullptr;
+    const int rc = srbd_qp_srbd_nmpc_plan_f64(h, batch, params, wplan, ls, settings, constraints,
+                                              sqp_max_loop, xs, us, x, alpha, it_step, cv_step);
+    if (rc) return rc;
+    srbd::AdvanceIo io{};
+    io.substeps = roll->substeps;
+    io.xs = xs;
+    io.us = us;
+    io.x = x;
+    io.wrench = roll->wrench ? roll->wrench + (size_t)t * 6 : nullptr;
+    io.wrench_stride = (long long)T * 6;
+    io.u_out = roll->u_log ? roll->u_log + (size_t)t * 12 : nullptr;
+    io.u_stride = (long long)T * 12;
+    io.x_out = roll->x_log ? roll->x_log + (size_t)(t + 1) * 12 : nullptr;
+    io.x_stride = (long long)(T + 1) * 12;
+    io.it_src = it_step;
+    io.cv_src = cv_step;
+    io.it_log = roll->sqp_iter_log ? roll->sqp_iter_log + t : nullptr;
+    io.cv_log = roll->converged_log ? roll->converged_log + t : nullptr;
+    io.log_stride = T;
+    e = srbd::launch_srbd_advance(*params, batch, N, io, wplan, strm);
+    if (e != hipSuccess) return device_error(e, "rollout: ");
+  }
+  e = hipStreamSynchronize(strm);
+  if (e != hipSuccess) return device_error(e, "rollout: ");
+  return SRBD_QP_OK;
 }
 
 int srbd_qp_solve_f32(srbd_qp_handle h, int batch, const srbd_qp_settings* st,

@@ -29,7 +29,8 @@ import numpy as np
 
 from .qp import OcpQpBatch
 
-__all__ = ["SrbdParams", "SrbdPlan", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier"]
+__all__ = ["SrbdParams", "SrbdPlan", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier",
+           "plant_step", "shift_guess"]
 
 
 @dataclass(frozen=True)
@@ -238,6 +239,58 @@ def shooting_dynamics(x, x_next, u, p: SrbdParams, plan: Optional[SrbdPlan] = No
     B = dt * jfu
     b = x_get - x_next  # b = -f, f = x_next - x_get (:194-197, :225-229)
     return A, B, b
+
+
+# ---------------------------------------------------------------------------
+# the closed loop between two NMPC steps (the C-ABI's srbd_qp_srbd_advance_f64)
+# ---------------------------------------------------------------------------
+def _rk4_step(x, u, p: SrbdParams, h: float, plan: Optional[SrbdPlan], wrench=None):
+    """One classical RK4 step of length h of xdot = f(x, u) + w: the operations of
+    shooting_dynamics' x_get, in its order.  wrench [..., 6] (torque, force; world frame) adds
+    wrench[0:3] to rows 3..5 and wrench[3:6] / mass to rows 9..11 of every slope."""
+    def slope(xa):
+        dx = continuous(xa, u, p, False, plan)[0]
+        if wrench is not None:
+            dx[..., 3:6] += wrench[..., 0:3]
+            dx[..., 9:12] += wrench[..., 3:6] / p.mass
+        return dx
+
+    k1 = slope(x)
+    k2 = slope(x + 0.5 * h * k1)
+    k3 = slope(x + 0.5 * h * k2)
+    k4 = slope(x + h * k3)
+    return x + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
+
+
+def plant_step(x, u, p: SrbdParams, foot_r=None, foot_l=None, wrench=None, substeps: int = 1):
+    """The plant over one control tick: x [B][12] after `substeps` RK4 steps of dt / substeps of
+    xdot = f(x, u) + w with the input u [B][12] held (applied as it is: nothing is clamped).
+    foot_r / foot_l [B][3]: the feet during the tick (None: SrbdParams'); wrench [B][6]: an
+    external torque and force on the body, world frame, held over the tick (None: none)."""
+    if substeps < 1:
+        raise ValueError("substeps must be at least 1")
+    feet = None if foot_r is None and foot_l is None else SrbdPlan(foot_r=foot_r, foot_l=foot_l)
+    h = p.dt / substeps
+    for _ in range(substeps):
+        x = _rk4_step(x, u, p, h, feet, wrench)
+    return x
+
+
+def shift_guess(xs, us, p: SrbdParams, plan: Optional[SrbdPlan] = None):
+    """The previous solution shifted by one stage, the warm start of the next tick: xs [B][N+1][12],
+    us [B][N][12] -> (xs', us') with xs'[k] = xs[k+1] (k < N), us'[k] = us[k+1] (k < N-1),
+    us'[N-1] = us[N-1] and xs'[N] one RK4 step of the model over dt from xs[N] with us[N-1] and
+    the feet of the plan's stage N-1, so the new last stage has no shooting defect.  xs'[0] is
+    the old xs[1], not the plant's state: the step forms x0 - xs[:, 0] itself."""
+    N = us.shape[1]
+    last = None
+    if plan is not None and (plan.foot_r is not None or plan.foot_l is not None):
+        last = SrbdPlan(foot_r=None if plan.foot_r is None else np.asarray(plan.foot_r)[:, N - 1],
+                        foot_l=None if plan.foot_l is None else np.asarray(plan.foot_l)[:, N - 1])
+    xN = _rk4_step(xs[:, N], us[:, N - 1], p, p.dt, last)
+    xs_new = np.concatenate([xs[:, 1:], xN[:, None]], axis=1)
+    us_new = np.concatenate([us[:, 1:], us[:, N - 1:]], axis=1)
+    return xs_new, us_new
 
 
 def friction_cone(p: SrbdParams):
