@@ -26,6 +26,10 @@
 //                 reusing the record (element-owned)
 //   F2  k = 0..N  corrector step, dt / dlam, alpha_prim / alpha_dual
 // RB + F1 and B2 + F2 run as one launch each (ipm_phase2_kernel).
+// Source: ipm_box_impl.h holds Ctx, ipm_phase (every phase, one `if constexpr (PH == ...)`
+// block each behind a shared prologue), the kernels and the launch sequence.  ipm_barrier.h is
+// the barrier algebra of one inequality pair (shared with ipm_latency.hip), ipm_soft_box.h the
+// soft-box algebra of the SOFT kernels (ipm_soft.hip).
 // Box bounds are dense per variable (include/srbd_qp.h), so bound i of u_k /
 // x_k lives on lane i next to u_k[i] / x_k[i]: every constraint operation is
 // lane-local and the barrier Hessian only touches the diagonals of R and Q.
@@ -50,8 +54,7 @@ namespace srbd {
 
 size_t ws_doubles_ipm(int N, int ng) {
   const int nch = (ng + kMaxDim - 1) / kMaxDim;
-  return ipm_f64::kQsSize +
-         (size_t)(N + 1) * ((size_t)kIpmStage + (size_t)nch * kGenChunk + (nch ? kGenVec : 0));
+  return ipm_f64::kQsSize + (size_t)(N + 1) * ipm_stage_stride(nch);
 }
 
 namespace {
@@ -132,7 +135,7 @@ hipError_t launch_gather_warm_apply(const float* ws32, size_t ws_qp, int N, int 
                                     double* u, double* pi, double* bars, hipStream_t s) {
   if (batch <= 0) return hipSuccess;
   const int nch = (ng + kMaxDim - 1) / kMaxDim;
-  const size_t stride = (size_t)kIpmStage + (size_t)nch * kGenChunk + (nch ? kGenVec : 0);
+  const size_t stride = ipm_stage_stride(nch);
   auto grid = [](size_t total) {
     const size_t blocks = (total + 255) / 256;
     return dim3((unsigned)(blocks < 8192 ? blocks : 8192));
@@ -150,7 +153,7 @@ hipError_t launch_gather_warm_bars(const float* ws32, size_t ws_qp, int N, int n
                                    int rows, double* dst, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   const int nch = (ng + kMaxDim - 1) / kMaxDim;
-  const size_t stride = (size_t)kIpmStage + (size_t)nch * kGenChunk + (nch ? kGenVec : 0);
+  const size_t stride = ipm_stage_stride(nch);
   const size_t total = (size_t)rows * (N + 1) * (96 + (size_t)nch * 48);
   const size_t blocks = (total + 255) / 256;
   hipLaunchKernelGGL(gather_warm_bars_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256),

@@ -2,13 +2,20 @@
 // ipm_box.hip (SRBD_REAL = double / float, namespace SRBD_NS), the way HPIPM
 // generates its d_ and s_ solvers from one source.  No include guard: included twice.
 // The kernel code is documented in ipm_box.hip.
+#include "ipm_barrier.h"
 
 namespace srbd {
 namespace SRBD_NS {
 
 using real = SRBD_REAL;
 
-constexpr real kThr0 = real(0.1);     // minimum initial slack (HPIPM init_var)
+// the barrier algebra of one inequality pair (ipm_barrier.h), in this precision
+using Side = barrier::Side<real>;
+using Bar = barrier::Bar<real>;
+using BarStep = barrier::BarStep<real>;
+using barrier::gsum, barrier::gmax, barrier::gmin, barrier::huge, barrier::step, barrier::nabs;
+using barrier::init_box, barrier::gamma_of, barrier::bar_step, barrier::ratio, barrier::aff_sums;
+constexpr real kThr0 = barrier::kThr0<real>, kStepTau = barrier::kStepTau<real>;
 
 // phase kernels (one launch each, per IPM iteration; see launch_ipm_box)
 constexpr int kPhInit = 0, kPhRB = 1, kPhF1 = 2, kPhB2 = 3, kPhF2 = 4, kPhOut = 5;
@@ -29,38 +36,6 @@ constexpr int kQsAlphaP = 0, kQsAlphaD = 1, kQsLastAmin = 2, kQsMu = 3, kQsMuSum
               // lq_fact 1 once a predictor's linear residual exceeded 1e-5), and the pending redo
               // of this iteration's factorization + predictor by LQ (lq_fact 1)
               kQsForceLq = 18, kQsLqRedo = 19, kQsSize = 20;
-constexpr real kStepTau = real(0.995);  // fraction to the boundary
-
-__device__ __forceinline__ real gsum(real v) {
-  v += __shfl_xor(v, 8, kGroup);
-  v += __shfl_xor(v, 4, kGroup);
-  v += __shfl_xor(v, 2, kGroup);
-  v += __shfl_xor(v, 1, kGroup);
-  return v;
-}
-__device__ __forceinline__ real gmax(real v) {
-  v = fmax(v, __shfl_xor(v, 8, kGroup));
-  v = fmax(v, __shfl_xor(v, 4, kGroup));
-  v = fmax(v, __shfl_xor(v, 2, kGroup));
-  v = fmax(v, __shfl_xor(v, 1, kGroup));
-  return v;
-}
-__device__ __forceinline__ real gmin(real v) {
-  v = fmin(v, __shfl_xor(v, 8, kGroup));
-  v = fmin(v, __shfl_xor(v, 4, kGroup));
-  v = fmin(v, __shfl_xor(v, 2, kGroup));
-  v = fmin(v, __shfl_xor(v, 1, kGroup));
-  return v;
-}
-// NaN, or too large to square in this precision (sqrt(max) / 1e4: 1.8e15 in fp32)
-__device__ __forceinline__ bool huge(real v) {
-  constexpr real kHuge = sizeof(real) == 4 ? real(1.8e15) : real(1.3e150);
-  return !(__builtin_fabs(v) < kHuge);
-}
-// v + a d, with a = 0 (no step taken) leaving v as it is whatever d holds
-__device__ __forceinline__ real step(real v, real a, real d) { return a != real(0.0) ? fmadd(a, d, v) : v; }
-// |v| propagating NaN (max with NaN would drop it)
-__device__ __forceinline__ real nabs(real v) { return v == v ? fabs(v) : real(__builtin_inf()); }
 
 template <typename T>
 __device__ __forceinline__ T dot12(const T (&a)[12], const T (&b)[12], T acc) {
@@ -71,10 +46,7 @@ __device__ __forceinline__ T dot12(const T (&a)[12], const T (&b)[12], T acc) {
   return acc;
 }
 
-// barrier state of one variable: lam_l, lam_u, t_l, t_u
-struct Bar {
-  real ll, lu, tl, tu;
-};
+// barrier state (Bar) and step (BarStep) of u_k's (which 0) / x_k's (1) bounds in the stage
 __device__ __forceinline__ Bar load_bar(const real* stk, int which, int i) {
   const real* p = stk + kStLam + which * 48;
   return Bar{p[i], p[12 + i], p[24 + i], p[36 + i]};
@@ -86,10 +58,6 @@ __device__ __forceinline__ void store_bar(real* stk, int which, int i, const Bar
   p[24 + i] = b.tl;
   p[36 + i] = b.tu;
 }
-// step of one variable's barrier pair: dt_l, dt_u, dlam_l, dlam_u
-struct BarStep {
-  real dtl, dtu, dll, dlu;
-};
 __device__ __forceinline__ BarStep load_bstep(const real* stk, int which, int i) {
   const real* p = stk + kStDlt + which * 48;
   return BarStep{p[i], p[12 + i], p[24 + i], p[36 + i]};
@@ -101,12 +69,6 @@ __device__ __forceinline__ void store_bstep(real* stk, int which, int i, const B
   p[24 + i] = d.dll;
   p[36 + i] = d.dlu;
 }
-
-// One inequality side on one variable (box bound, dense per variable).
-struct Side {
-  real lb, ub;   // bounds
-  real ml, mu;   // 1 if the lower / upper bound is active, else 0
-};
 
 // Barrier state of one variable / row from a warm-start buffer (p[0] lam_l, p[12] lam_u,
 // p[24] t_l, p[36] t_u): the stored values on active sides, the cold init's defaults
@@ -156,7 +118,7 @@ __device__ __forceinline__ void rec_copy(real* rec, const real* img, int lane) {
   for (int p = lane; p < kPieces; p += kGroup) d[p] = s[p];
 }
 
-template <bool FULL, int GEN>
+template <int GEN>
 struct Ctx {
   int N, nx, nu, lane, qp;
   bool isv;
@@ -209,9 +171,10 @@ struct Ctx {
   __device__ real* pi() const { return bpi + oN1() * nx; }
   __device__ real* ws() const { return bws + oq() * ws_qp; }
 
-  __device__ size_t nxx() const { return FULL ? 144 : (size_t)nx * nx; }
-  __device__ size_t nxu() const { return FULL ? 144 : (size_t)nx * nu; }
-  __device__ size_t nuu() const { return FULL ? 144 : (size_t)nu * nu; }
+  // (12 x 12 stages only: smaller problems arrive embedded by pad.hip)
+  __device__ size_t nxx() const { return 144; }
+  __device__ size_t nxu() const { return 144; }
+  __device__ size_t nuu() const { return 144; }
   __device__ real* st(int k) const {
     return ws() + kQsSize + (size_t)k * (GEN ? stride : (size_t)kIpmStage);
   }
@@ -278,41 +241,22 @@ struct Ctx {
     });
   }
 
-  // ---- column-owned loads (lane = column), zero padded ----
+  // ---- column-owned loads (lane = column) of a 12 x 12 block ----
   __device__ void col(const real* blk, int rows, int c, bool ok, real (&v)[12]) const {
-    if constexpr (FULL) {
-      load12(blk + c * 12, v);
-    } else {
-      load_col_pad(blk + (size_t)c * rows, rows, ok, v);
-    }
+    load12(blk + c * 12, v);
   }
-  // ---- row-owned loads (lane = row) of a column-major (rows x cols) block ----
+  // ---- row-owned loads (lane = row) of a column-major 12 x 12 block ----
   __device__ void row(const real* blk, int rows, int cols, int rw, bool ok, real (&v)[12]) const {
     sfor<0, 12>([&](auto j) {
       constexpr int J = decltype(j)::value;
-      if constexpr (FULL) {
-        v[J] = blk[rw + J * 12];
-      } else {
-        v[J] = (ok && J < cols) ? blk[(size_t)rw + (size_t)J * rows] : real(0.0);
-      }
+      v[J] = blk[rw + J * 12];
     });
   }
-  // element i of a length-n vector (0 beyond n)
-  __device__ real el(const real* v, int n, int i) const {
-    if constexpr (FULL) {
-      return i < 12 ? v[i] : real(0.0);
-    } else {
-      return i < n ? v[i] : real(0.0);
-    }
-  }
+  // element i of a length-12 vector (0 beyond it)
+  __device__ real el(const real* v, int n, int i) const { return i < 12 ? v[i] : real(0.0); }
   // per-variable barrier state exists only for the bound families that are given
   // (which 0: u, 1: x): absent ones are neither loaded nor stored
-  // (FULL only: the generic-size kernels keep the unconditional accesses, their
-  // spill-heavy code generation faulted with the uniform branches added)
-  __device__ bool has_bars(int which) const {
-    if constexpr (!FULL) return true;
-    return which ? blbx != nullptr : blbu != nullptr;
-  }
+  __device__ bool has_bars(int which) const { return which ? blbx != nullptr : blbu != nullptr; }
   __device__ Bar bar(const real* stk, int which, int i) const {
     return has_bars(which) ? load_bar(stk, which, i) : Bar{real(0.0), real(0.0), real(1.0), real(1.0)};
   }
@@ -374,300 +318,7 @@ __device__ __forceinline__ void store_gstep(real* g, int i, const BarStep& d) {
 }
 constexpr int kGenVal = 96;
 
-
-// Gamma (Hessian add) and gamma (gradient add) of one variable:
-// Gamma = lam_l/t_l + lam_u/t_u,
-// gamma = (rm_l + lam_l rd_l)/t_l - (rm_u + lam_u rd_u)/t_u, with
-// rm = lam t + extra - sigma_mu (extra = dlam_aff dt_aff in the corrector).
-__device__ __forceinline__ void gamma_of(const Side& s, const Bar& b, real v, real ext_l,
-                                         real ext_u, real smu, real& G, real& g) {
-  G = real(0.0);
-  g = real(0.0);
-  if (s.ml != real(0.0)) {
-    const real rd = v - s.lb - b.tl;
-    const real rm = b.ll * b.tl + ext_l - smu;
-    G += b.ll / b.tl;
-    g += (rm + b.ll * rd) / b.tl;
-  }
-  if (s.mu != real(0.0)) {
-    const real rd = s.ub - v - b.tu;
-    const real rm = b.lu * b.tu + ext_u - smu;
-    G += b.lu / b.tu;
-    g -= (rm + b.lu * rd) / b.tu;
-  }
-}
-
-// dt / dlam of one variable given its primal step dv.
-__device__ __forceinline__ BarStep bar_step(const Side& s, const Bar& b, real v, real dv,
-                                            real ext_l, real ext_u, real smu) {
-  BarStep d{real(0.0), real(0.0), real(0.0), real(0.0)};
-  if (s.ml != real(0.0)) {
-    const real rd = v - s.lb - b.tl;
-    d.dtl = rd + dv;
-    d.dll = -(b.ll * b.tl + ext_l - smu + b.ll * d.dtl) / b.tl;
-  }
-  if (s.mu != real(0.0)) {
-    const real rd = s.ub - v - b.tu;
-    d.dtu = rd - dv;
-    d.dlu = -(b.lu * b.tu + ext_u - smu + b.lu * d.dtu) / b.tu;
-  }
-  return d;
-}
-
-__device__ __forceinline__ void ratio(const Side& s, const Bar& b, const BarStep& d, real& ap,
-                                      real& ad) {
-  if (s.ml != real(0.0)) {
-    if (d.dtl < real(0.0)) ap = fmin(ap, -b.tl / d.dtl);
-    if (d.dll < real(0.0)) ad = fmin(ad, -b.ll / d.dll);
-  }
-  if (s.mu != real(0.0)) {
-    if (d.dtu < real(0.0)) ap = fmin(ap, -b.tu / d.dtu);
-    if (d.dlu < real(0.0)) ad = fmin(ad, -b.lu / d.dlu);
-  }
-}
-
-// predictor sums for mu_aff: s1 += lam dt + t dlam, s2 += dlam dt (active sides)
-__device__ __forceinline__ void aff_sums(const Side& s, const Bar& b, const BarStep& d, real& s1,
-                                         real& s2) {
-  if (s.ml != real(0.0)) {
-    s1 += b.ll * d.dtl + b.tl * d.dll;
-    s2 += d.dll * d.dtl;
-  }
-  if (s.mu != real(0.0)) {
-    s1 += b.lu * d.dtu + b.tu * d.dlu;
-    s2 += d.dlu * d.dtu;
-  }
-}
-
-// ---- soft boxes (SOFT kernels only; HPIPM's Zl / Zu / zl / zu / lls / lus) ----
-// A soft bound on v has a slack s >= sb on each active side, penalised by 1/2 Z s^2 + z s:
-//   t = w + s - bound (w = v - lb below, ub - v above),  t_s = s - sb,
-//   r_s = Z s + z - lam - lam_s                 (stationarity in s),
-//   dlam = -g - Gamma (dw + ds),  dlam_s = -g_s - Gamma_s ds   (Gamma = lam / t, g as gamma_of).
-// The slack's row Z ds - dlam - dlam_s + r_s = 0 is solved lane-locally,
-//   ds = -(r_s + g + g_s + Gamma dw) / Zt,  Zt = Z + Gamma + Gamma_s,
-// which leaves the variable's own row with
-//   Gamma_eff = Gamma (Z + Gamma_s) / Zt,  g_eff = g - Gamma (r_s + g + g_s) / Zt
-// in place of Gamma, g: the Riccati recursion sees a diagonal barrier Hessian as before.
-struct SoftIn {   // the variable's soft data: on = 1 if soft, penalties, slack bounds
-  real on, Zl, Zu, zl, zu, bl, bu;
-};
-struct SoftSt {   // slacks, and the slack bounds' t and lam
-  real sl, su, tl, tu, ll, lu;
-};
-struct SoftStep {
-  real dsl, dsu, dtl, dtu, dll, dlu;
-};
-__device__ __forceinline__ SoftSt load_soft(const real* p, int i) {
-  p += kSoftSt;
-  return SoftSt{p[i], p[12 + i], p[24 + i], p[36 + i], p[48 + i], p[60 + i]};
-}
-__device__ __forceinline__ void store_soft(real* p, int i, const SoftSt& s) {
-  p += kSoftSt;
-  p[i] = s.sl; p[12 + i] = s.su; p[24 + i] = s.tl; p[36 + i] = s.tu; p[48 + i] = s.ll; p[60 + i] = s.lu;
-}
-__device__ __forceinline__ SoftStep load_sstep(const real* p, int i) {
-  p += kSoftDlt;
-  return SoftStep{p[i], p[12 + i], p[24 + i], p[36 + i], p[48 + i], p[60 + i]};
-}
-__device__ __forceinline__ void store_sstep(real* p, int i, const SoftStep& d) {
-  p += kSoftDlt;
-  p[i] = d.dsl; p[12 + i] = d.dsu; p[24 + i] = d.dtl; p[36 + i] = d.dtu; p[48 + i] = d.dll; p[60 + i] = d.dlu;
-}
-// The soft arrays of one QP (dense per variable like the bounds; every load at a valid
-// address, masked after: see Ctx::side_at)
-struct SoftView {
-  const SoftArgsT<real>& s;
-  int N, nx, nu;
-  size_t q;
-  __device__ real* st(int k, int which) const {
-    return s.sws + q * s.sws_qp + (size_t)k * kSoftStage + which * kSoftFam;
-  }
-  __device__ static SoftIn in_at(const real* soft, const real* Zl, const real* Zu, const real* zl,
-                                 const real* zu, const real* bl, const real* bu, size_t o, bool ok) {
-    const real m = soft[o], a = Zl[o], b = Zu[o], c = zl[o], d = zu[o];
-    const real e = (bl ? bl : soft)[o], f = (bu ? bu : soft)[o];
-    const bool on = ok && m != real(0.0);
-    const real z = real(0.0);
-    return SoftIn{on ? real(1.0) : z, on ? a : z, on ? b : z, on ? c : z, on ? d : z,
-                  on && bl ? e : z, on && bu ? f : z};
-  }
-  __device__ SoftIn in_u(int k, int i) const {
-    if (!s.soft_u) return SoftIn{0, 0, 0, 0, 0, 0, 0};
-    const bool ok = i < nu && k < N;
-    const size_t o = (q * N + (k < N ? k : N - 1)) * nu + (ok ? i : 0);
-    return in_at(s.soft_u, s.Zl_u, s.Zu_u, s.zl_u, s.zu_u, s.lls_u, s.lus_u, o, ok);
-  }
-  __device__ SoftIn in_x(int k, int i) const {
-    if (!s.soft_x) return SoftIn{0, 0, 0, 0, 0, 0, 0};
-    const bool ok = i < nx && k > 0;  // stage-0 x bounds dropped
-    const size_t o = (q * (N + 1) + k) * nx + (ok ? i : 0);
-    return in_at(s.soft_x, s.Zl_x, s.Zu_x, s.zl_x, s.zu_x, s.lls_x, s.lus_x, o, ok);
-  }
-};
-// One active side of a soft variable in side-local terms (w, lam, t: the bound's pair; s, ts,
-// ls: the slack and its bound's pair; ext / exs: the corrector's predictor products).
-struct SoftOne {
-  real Gl, rd, rm, rds, rms, rsum, Zt, Geff, geff;
-};
-__device__ __forceinline__ SoftOne soft_one(real w, real lam, real t, real s, real ts, real ls, real Z,
-                                            real z, real sb, real ext, real exs, real smu) {
-  SoftOne o;
-  o.rd = w + s - t;
-  o.rm = lam * t + ext - smu;
-  o.Gl = lam / t;
-  const real gl = (o.rm + lam * o.rd) / t;
-  o.rds = s - sb - ts;
-  o.rms = ls * ts + exs - smu;
-  const real Gs = ls / ts;
-  const real gs = (o.rms + ls * o.rds) / ts;
-  o.rsum = Z * s + z - lam - ls + gl + gs;
-  o.Zt = Z + o.Gl + Gs;
-  o.Geff = o.Gl * (Z + Gs) / o.Zt;
-  o.geff = gl - o.Gl * o.rsum / o.Zt;
-  return o;
-}
-// gamma_of for a variable that may be soft
-__device__ __forceinline__ void gamma_soft(const Side& s, const Bar& b, const SoftIn& si, const SoftSt& ss,
-                                           real v, real ext_l, real ext_u, real exs_l, real exs_u, real smu,
-                                           real& G, real& g) {
-  if (si.on == real(0.0)) {
-    gamma_of(s, b, v, ext_l, ext_u, smu, G, g);
-    return;
-  }
-  G = real(0.0);
-  g = real(0.0);
-  if (s.ml != real(0.0)) {
-    const SoftOne o = soft_one(v - s.lb, b.ll, b.tl, ss.sl, ss.tl, ss.ll, si.Zl, si.zl, si.bl, ext_l, exs_l, smu);
-    G += o.Geff;
-    g += o.geff;
-  }
-  if (s.mu != real(0.0)) {
-    const SoftOne o = soft_one(s.ub - v, b.lu, b.tu, ss.su, ss.tu, ss.lu, si.Zu, si.zu, si.bu, ext_u, exs_u, smu);
-    G += o.Geff;
-    g -= o.geff;
-  }
-}
-// bar_step for a variable that may be soft: ds from dv, then dt / dlam of both pairs
-__device__ __forceinline__ void soft_step(const Side& s, const Bar& b, const SoftIn& si, const SoftSt& ss,
-                                          real v, real dv, real ext_l, real ext_u, real exs_l, real exs_u,
-                                          real smu, BarStep& d, SoftStep& e) {
-  e = SoftStep{0, 0, 0, 0, 0, 0};
-  if (si.on == real(0.0)) {
-    d = bar_step(s, b, v, dv, ext_l, ext_u, smu);
-    return;
-  }
-  d = BarStep{0, 0, 0, 0};
-  if (s.ml != real(0.0)) {
-    const SoftOne o = soft_one(v - s.lb, b.ll, b.tl, ss.sl, ss.tl, ss.ll, si.Zl, si.zl, si.bl, ext_l, exs_l, smu);
-    e.dsl = -(o.rsum + o.Gl * dv) / o.Zt;
-    d.dtl = o.rd + dv + e.dsl;
-    d.dll = -(o.rm + b.ll * d.dtl) / b.tl;
-    e.dtl = o.rds + e.dsl;
-    e.dll = -(o.rms + ss.ll * e.dtl) / ss.tl;
-  }
-  if (s.mu != real(0.0)) {
-    const SoftOne o = soft_one(s.ub - v, b.lu, b.tu, ss.su, ss.tu, ss.lu, si.Zu, si.zu, si.bu, ext_u, exs_u, smu);
-    e.dsu = -(o.rsum - o.Gl * dv) / o.Zt;
-    d.dtu = o.rd - dv + e.dsu;
-    d.dlu = -(o.rm + b.lu * d.dtu) / b.tu;
-    e.dtu = o.rds + e.dsu;
-    e.dlu = -(o.rms + ss.lu * e.dtu) / ss.tu;
-  }
-}
-// the slack bounds' pairs in the step ratios and the predictor sums
-__device__ __forceinline__ void ratio_soft(const Side& s, const SoftIn& si, const SoftSt& ss, const SoftStep& e,
-                                           real& ap, real& ad) {
-  if (si.on == real(0.0)) return;
-  if (s.ml != real(0.0)) {
-    if (e.dtl < real(0.0)) ap = fmin(ap, -ss.tl / e.dtl);
-    if (e.dll < real(0.0)) ad = fmin(ad, -ss.ll / e.dll);
-  }
-  if (s.mu != real(0.0)) {
-    if (e.dtu < real(0.0)) ap = fmin(ap, -ss.tu / e.dtu);
-    if (e.dlu < real(0.0)) ad = fmin(ad, -ss.lu / e.dlu);
-  }
-}
-__device__ __forceinline__ void aff_soft(const Side& s, const SoftIn& si, const SoftSt& ss, const SoftStep& e,
-                                         real& s1, real& s2) {
-  if (si.on == real(0.0)) return;
-  if (s.ml != real(0.0)) {
-    s1 += ss.ll * e.dtl + ss.tl * e.dll;
-    s2 += e.dll * e.dtl;
-  }
-  if (s.mu != real(0.0)) {
-    s1 += ss.lu * e.dtu + ss.tu * e.dlu;
-    s2 += e.dlu * e.dtu;
-  }
-}
-__device__ __forceinline__ bool huge_soft(const SoftStep& e) {
-  return huge(e.dsl) || huge(e.dsu) || huge(e.dtl) || huge(e.dtu) || huge(e.dll) || huge(e.dlu);
-}
-// RB's box terms of one variable that may be soft: the multipliers in its gradient residual
-// rg, and the norms of res_d (md), res_m (mm, musum), the slacks' stationarity r_s (mg) and
-// the slack penalty (obj)
-__device__ __forceinline__ void rb_soft_terms(const Side& s, const Bar& b, const SoftIn& si, const SoftSt& ss,
-                                              real v, real& rg, real& mg, real& md, real& mm, real& musum,
-                                              real& obj) {
-  const bool on = si.on != real(0.0);
-  if (s.ml != real(0.0)) {
-    rg -= b.ll;
-    const real rd = v + (on ? ss.sl : real(0.0)) - s.lb - b.tl, rm = b.ll * b.tl;
-    md = fmax(md, nabs(rd));
-    mm = fmax(mm, nabs(rm));
-    musum += rm;
-    if (on) {
-      const real rms = ss.ll * ss.tl;
-      md = fmax(md, nabs(ss.sl - si.bl - ss.tl));
-      mm = fmax(mm, nabs(rms));
-      musum += rms;
-      mg = fmax(mg, nabs(si.Zl * ss.sl + si.zl - b.ll - ss.ll));
-      obj += ss.sl * (real(0.5) * si.Zl * ss.sl + si.zl);
-    }
-  }
-  if (s.mu != real(0.0)) {
-    rg += b.lu;
-    const real rd = s.ub - v + (on ? ss.su : real(0.0)) - b.tu, rm = b.lu * b.tu;
-    md = fmax(md, nabs(rd));
-    mm = fmax(mm, nabs(rm));
-    musum += rm;
-    if (on) {
-      const real rms = ss.lu * ss.tu;
-      md = fmax(md, nabs(ss.su - si.bu - ss.tu));
-      mm = fmax(mm, nabs(rms));
-      musum += rms;
-      mg = fmax(mg, nabs(si.Zu * ss.su + si.zu - b.lu - ss.lu));
-      obj += ss.su * (real(0.5) * si.Zu * ss.su + si.zu);
-    }
-  }
-}
-// Cold start of a soft variable (the init of the same problem with its slacks written as
-// inputs boxed below by sb and the bound as a general row): v stays where it is, s = max(0,
-// sb + thr0), t_s = s - sb, t = max(w + s, thr0), lam = mu0 / t for both pairs.  Returns
-// the number of slack-bound pairs (one per active side).
-__device__ __forceinline__ real soft_init(const Side& s, const SoftIn& si, real v, real mu0, Bar& b, SoftSt& ss) {
-  ss = SoftSt{real(0.0), real(0.0), real(1.0), real(1.0), real(0.0), real(0.0)};
-  if (si.on == real(0.0)) return real(0.0);
-  b = Bar{real(0.0), real(0.0), real(1.0), real(1.0)};
-  real n = real(0.0);
-  if (s.ml != real(0.0)) {
-    ss.sl = fmax(real(0.0), si.bl + kThr0);
-    ss.tl = ss.sl - si.bl;
-    ss.ll = mu0 / ss.tl;
-    b.tl = fmax(v - s.lb + ss.sl, kThr0);
-    b.ll = mu0 / b.tl;
-    n += real(1.0);
-  }
-  if (s.mu != real(0.0)) {
-    ss.su = fmax(real(0.0), si.bu + kThr0);
-    ss.tu = ss.su - si.bu;
-    ss.lu = mu0 / ss.tu;
-    b.tu = fmax(s.ub - v + ss.su, kThr0);
-    b.lu = mu0 / b.tu;
-    n += real(1.0);
-  }
-  return n;
-}
+#include "ipm_soft_box.h"
 
 // gather an element-owned value (lane i < 12 holds v_i) into VL's registers
 __device__ __forceinline__ void gather12(real v, real (&out)[12]) {
@@ -711,9 +362,9 @@ struct SoftProblemArgs : ProblemArgsT<real> {
 };
 template <bool SOFT>
 using IpmArgs = std::conditional_t<SOFT, SoftProblemArgs, ProblemArgsT<real>>;
-template <bool FULL, int GEN, int PH, bool SQRT = false, int LQ = 0, bool SOFT = false>
+template <int GEN, int PH, bool SQRT = false, int LQ = 0, bool SOFT = false>
 __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
-  static_assert(!SOFT || (FULL && GEN == 0 && LQ == 0 && sizeof(real) == 8), "soft boxes: fp64 box kernels");
+  static_assert(!SOFT || (GEN == 0 && LQ == 0 && sizeof(real) == 8), "soft boxes: fp64 box kernels");
   // the refinement check runs stage-parallel: group g on QP slot g / (N + 1), stage
   // g % (N + 1) (its rows are independent across stages); every other phase: one QP per group
   int kst = 0;
@@ -729,13 +380,12 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
   const int lane = threadIdx.x & (kGroup - 1);
   if (qp < 0) return;
   const int N = a.N;
-  const int nx = FULL ? 12 : a.nx;
-  const int nu = FULL ? 12 : a.nu;
+  const int nx = 12, nu = 12;  // (launch() admits nothing else)
   const int col = lane < kMaxDim ? lane : kMaxDim - 1;
   const int li = lane < kMaxDim ? lane : 0;  // element index used for addressing
   const bool xel = lane < nx, uel = lane < nu;
 
-  Ctx<FULL, GEN> c;
+  Ctx<GEN> c;
   c.N = N;
   c.nx = nx;
   c.nu = nu;
@@ -744,7 +394,7 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
   c.qp = qp;
   c.ng = a.ng;
   c.nch = (a.ng + kMaxDim - 1) / kMaxDim;
-  c.stride = (size_t)kIpmStage + (size_t)c.nch * kGenChunk + (c.nch ? kGenVec : 0);
+  c.stride = ipm_stage_stride(c.nch);
   c.ws_qp = a.ws_qp;
   c.bA = a.A; c.bB = a.B; c.bb = a.b; c.bQ = a.Q; c.bS = a.S; c.bR = a.R; c.bq = a.q; c.br = a.r;
   c.bx0 = a.x0;
@@ -832,77 +482,162 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
     }
   };
 
-
   real* const qs = c.ws();  // per-QP scalar state (kQs*)
   if constexpr (PH == kPhInit) {
-  // =================== init (var_init_scheme 0, relative form) ===================
-  real ncl = real(0.0);
-  // warm_start 2: continue from a whole iterate -- x, u, pi from the solution buffers, the
-  // barrier state from a.warm_bars (HPIPM's warm_start = 2 level; used by the fp64
-  // continuation of srbd_qp_settings.f64_rescue).  A non-finite value or a t <= 0 anywhere
-  // in the QP falls back to the cold start.
-  const size_t warm_w = 96 + (size_t)c.nch * 48;
-  const real* wb = a.warm_start == 2 && a.warm_bars
-                       ? a.warm_bars + (size_t)c.oq() * (size_t)(N + 1) * warm_w
-                       : nullptr;
-  bool cont = false;
-  if (wb) {
-    int bad = 0;
-    // an active side needs a finite lam > 0 and t > 0 (a multiplier that underflowed to 0
-    // would pin the fraction-to-boundary step at 0); inactive sides and absent families
-    // are not read (warm_bar substitutes the cold defaults there)
-    auto chk = [&](real v, bool pos) { bad |= !__builtin_isfinite(v) || (pos && !(v > real(0.0))); };
-    auto chk_bar = [&](const real* p, const Side& s) {
-      if (s.ml != real(0.0)) {
-        chk(p[0], true);
-        chk(p[24], true);
+    // =================== init (var_init_scheme 0, relative form) ===================
+    real ncl = real(0.0);
+    // warm_start 2: continue from a whole iterate -- x, u, pi from the solution buffers, the
+    // barrier state from a.warm_bars (HPIPM's warm_start = 2 level; used by the fp64
+    // continuation of srbd_qp_settings.f64_rescue).  A non-finite value or a t <= 0 anywhere
+    // in the QP falls back to the cold start.
+    const size_t warm_w = 96 + (size_t)c.nch * 48;
+    const real* wb = a.warm_start == 2 && a.warm_bars
+                         ? a.warm_bars + (size_t)c.oq() * (size_t)(N + 1) * warm_w
+                         : nullptr;
+    bool cont = false;
+    if (wb) {
+      int bad = 0;
+      // an active side needs a finite lam > 0 and t > 0 (a multiplier that underflowed to 0
+      // would pin the fraction-to-boundary step at 0); inactive sides and absent families
+      // are not read (warm_bar substitutes the cold defaults there)
+      auto chk = [&](real v, bool pos) { bad |= !__builtin_isfinite(v) || (pos && !(v > real(0.0))); };
+      auto chk_bar = [&](const real* p, const Side& s) {
+        if (s.ml != real(0.0)) {
+          chk(p[0], true);
+          chk(p[24], true);
+        }
+        if (s.mu != real(0.0)) {
+          chk(p[12], true);
+          chk(p[36], true);
+        }
+      };
+      for (int k = 0; k <= N && lane < kMaxDim; ++k) {
+        const real* w = wb + (size_t)k * warm_w;
+        if (k < N) chk_bar(w + lane, c.side_u(k, lane));  // (no u_N)
+        chk_bar(w + 48 + lane, c.side_x(k, lane));
+        for (int ch = 0; ch < c.nch; ++ch) chk_bar(w + 96 + ch * 48 + lane, c.side_g(k, ch, lane));
+        if (k < N && uel) chk(c.u()[(size_t)k * nu + lane], false);
+        if (k > 0 && xel) {
+          chk(c.x()[(size_t)k * nx + lane], false);
+          chk(c.pi()[(size_t)k * nx + lane], false);
+        }
       }
-      if (s.mu != real(0.0)) {
-        chk(p[12], true);
-        chk(p[36], true);
-      }
-    };
-    for (int k = 0; k <= N && lane < kMaxDim; ++k) {
-      const real* w = wb + (size_t)k * warm_w;
-      if (k < N) chk_bar(w + lane, c.side_u(k, lane));  // (no u_N)
-      chk_bar(w + 48 + lane, c.side_x(k, lane));
-      for (int ch = 0; ch < c.nch; ++ch) chk_bar(w + 96 + ch * 48 + lane, c.side_g(k, ch, lane));
-      if (k < N && uel) chk(c.u()[(size_t)k * nu + lane], false);
-      if (k > 0 && xel) {
-        chk(c.x()[(size_t)k * nx + lane], false);
-        chk(c.pi()[(size_t)k * nx + lane], false);
+      cont = gsum(real(bad)) == real(0.0);
+    }
+    if (cont) {
+      for (int k = 0; k <= N; ++k) {
+        real* stk = c.st(k);
+        const real* w = wb + (size_t)k * warm_w;
+        if (lane < kMaxDim) {
+          store_bar(stk, 1, lane, warm_bar(w + 48 + lane, c.side_x(k, lane)));
+          store_bar(stk, 0, lane, k < N ? warm_bar(w + lane, c.side_u(k, lane))
+                                        : Bar{real(0.0), real(0.0), real(1.0), real(1.0)});
+        }
+        const real ui = (k < N && uel) ? c.u()[(size_t)k * nu + li] : real(0.0);
+        real xi;
+        if (k == 0) {
+          xi = xel ? c.x0()[li] : real(0.0);
+          if (xel) {
+            c.x()[lane] = xi;
+            c.pi()[lane] = real(0.0);
+          }
+        } else {
+          xi = xel ? c.x()[(size_t)k * nx + li] : real(0.0);
+        }
+        if (k < N) {
+          const Side s = c.side_u(k, lane);
+          ncl += s.ml + s.mu;
+        }
+        {
+          const Side s = c.side_x(k, lane);
+          ncl += s.ml + s.mu;
+        }
+        if constexpr (GEN) {
+          real bxi[12], bui[12];
+          gather12(xi, bxi);
+          gather12(ui, bui);
+          for (int ch = 0; ch < c.nch; ++ch) {
+            const real v = c.g_row_dot(k, ch, lane, bxi, bui);
+            const Side s = c.side_g(k, ch, lane);
+            ncl += s.ml + s.mu;
+            if (lane < kMaxDim) {
+              real* g = c.gs(k, ch);
+              store_gbar(g, lane, warm_bar(w + 96 + ch * 48 + lane, s));
+              store_gstep(g, lane, BarStep{0, 0, 0, 0});
+              g[kGenVal + lane] = v;
+            }
+          }
+        }
+        if (lane < kMaxDim) {
+          stk[kStStep + lane] = real(0.0);
+          stk[kStStep + 12 + lane] = real(0.0);
+          stk[kStStep + 24 + lane] = real(0.0);
+          store_bstep(stk, 0, lane, BarStep{0, 0, 0, 0});
+          store_bstep(stk, 1, lane, BarStep{0, 0, 0, 0});
+        }
       }
     }
-    cont = gsum(real(bad)) == real(0.0);
-  }
-  if (cont) {
-    for (int k = 0; k <= N; ++k) {
+    for (int k = 0; k <= N && !cont; ++k) {
       real* stk = c.st(k);
-      const real* w = wb + (size_t)k * warm_w;
-      if (lane < kMaxDim) {
-        store_bar(stk, 1, lane, warm_bar(w + 48 + lane, c.side_x(k, lane)));
-        store_bar(stk, 0, lane, k < N ? warm_bar(w + lane, c.side_u(k, lane))
-                                      : Bar{real(0.0), real(0.0), real(1.0), real(1.0)});
-      }
-      const real ui = (k < N && uel) ? c.u()[(size_t)k * nu + li] : real(0.0);
-      real xi;
-      if (k == 0) {
-        xi = xel ? c.x0()[li] : real(0.0);
-        if (xel) {
-          c.x()[lane] = xi;
-          c.pi()[lane] = real(0.0);
-        }
-      } else {
-        xi = xel ? c.x()[(size_t)k * nx + li] : real(0.0);
-      }
+      real ui = real(0.0), xi = real(0.0);  // initial u_k, x_k (element-owned)
+      // u_k
       if (k < N) {
+        real v = (a.warm_start && uel) ? c.u()[(size_t)k * nu + li] : real(0.0);
         const Side s = c.side_u(k, lane);
+        Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
+        [[maybe_unused]] SoftIn si{0, 0, 0, 0, 0, 0, 0};  // (a soft variable is not projected)
+        if constexpr (SOFT) si = SoftView{a.soft, N, nx, nu, c.oq()}.in_u(k, lane);
+        if (si.on == real(0.0)) bb = init_box(s, v, a.mu0);
         ncl += s.ml + s.mu;
+        if constexpr (SOFT) {
+          SoftSt ss;
+          ncl += soft_init(s, si, v, a.mu0, bb, ss);
+          if (lane < kMaxDim) {
+            real* sp = SoftView{a.soft, N, nx, nu, c.oq()}.st(k, 0);
+            store_soft(sp, lane, ss);
+            store_sstep(sp, lane, SoftStep{0, 0, 0, 0, 0, 0});
+          }
+        }
+        if (lane < kMaxDim) store_bar(stk, 0, lane, bb);
+        if (uel) c.u()[(size_t)k * nu + lane] = v;
+        ui = uel ? v : real(0.0);
       }
+      // x_k
       {
+        real v;
+        if (k == 0) {
+          v = xel ? c.x0()[li] : real(0.0);
+        } else {
+          v = (a.warm_start && xel) ? c.x()[(size_t)k * nx + li] : real(0.0);
+        }
         const Side s = c.side_x(k, lane);
+        Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
+        [[maybe_unused]] SoftIn si{0, 0, 0, 0, 0, 0, 0};
+        if constexpr (SOFT) si = SoftView{a.soft, N, nx, nu, c.oq()}.in_x(k, lane);
+        if (si.on == real(0.0)) bb = init_box(s, v, a.mu0);
         ncl += s.ml + s.mu;
+        if constexpr (SOFT) {
+          SoftSt ss;
+          ncl += soft_init(s, si, v, a.mu0, bb, ss);
+          if (lane < kMaxDim) {
+            const SoftView sv{a.soft, N, nx, nu, c.oq()};
+            store_soft(sv.st(k, 1), lane, ss);
+            store_sstep(sv.st(k, 1), lane, SoftStep{0, 0, 0, 0, 0, 0});
+            if (k == N) {  // (no u_N: its rows hold the defaults)
+              store_soft(sv.st(N, 0), lane, SoftSt{0, 0, 1, 1, 0, 0});
+              store_sstep(sv.st(N, 0), lane, SoftStep{0, 0, 0, 0, 0, 0});
+            }
+          }
+        }
+        if (lane < kMaxDim) store_bar(stk, 1, lane, bb);
+        if (xel) {
+          c.x()[(size_t)k * nx + lane] = v;
+          c.pi()[(size_t)k * nx + lane] = real(0.0);
+        }
+        xi = xel ? v : real(0.0);
       }
+      // general rows: t = max(v - lg, thr0), max(ug - v, thr0) at the initial
+      // x_k / u_k (no projection possible), lam = mu0 / t
       if constexpr (GEN) {
         real bxi[12], bui[12];
         gather12(xi, bxi);
@@ -910,16 +645,26 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
         for (int ch = 0; ch < c.nch; ++ch) {
           const real v = c.g_row_dot(k, ch, lane, bxi, bui);
           const Side s = c.side_g(k, ch, lane);
+          Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
+          if (s.ml != real(0.0)) {
+            bb.tl = fmax(v - s.lb, kThr0);
+            bb.ll = a.mu0 / bb.tl;
+          }
+          if (s.mu != real(0.0)) {
+            bb.tu = fmax(s.ub - v, kThr0);
+            bb.lu = a.mu0 / bb.tu;
+          }
           ncl += s.ml + s.mu;
           if (lane < kMaxDim) {
             real* g = c.gs(k, ch);
-            store_gbar(g, lane, warm_bar(w + 96 + ch * 48 + lane, s));
+            store_gbar(g, lane, bb);
             store_gstep(g, lane, BarStep{0, 0, 0, 0});
             g[kGenVal + lane] = v;
           }
         }
       }
       if (lane < kMaxDim) {
+        // zero step: the first RU pass applies nothing
         stk[kStStep + lane] = real(0.0);
         stk[kStStep + 12 + lane] = real(0.0);
         stk[kStStep + 24 + lane] = real(0.0);
@@ -927,175 +672,18 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
         store_bstep(stk, 1, lane, BarStep{0, 0, 0, 0});
       }
     }
-  }
-  for (int k = 0; k <= N && !cont; ++k) {
-    real* stk = c.st(k);
-    real ui = real(0.0), xi = real(0.0);  // initial u_k, x_k (element-owned)
-    // u_k
-    if (k < N) {
-      real v = (a.warm_start && uel) ? c.u()[(size_t)k * nu + li] : real(0.0);
-      const Side s = c.side_u(k, lane);
-      Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
-      [[maybe_unused]] SoftIn si{0, 0, 0, 0, 0, 0, 0};  // (a soft variable is not projected)
-      if constexpr (SOFT) si = SoftView{a.soft, N, nx, nu, c.oq()}.in_u(k, lane);
-      if (si.on == real(0.0) && (s.ml != real(0.0) || s.mu != real(0.0))) {
-        real tl = v - s.lb, tu = s.ub - v;
-        if (s.ml != real(0.0) && s.mu != real(0.0)) {
-          if (tl < kThr0) {
-            if (tu < kThr0) {
-              v = real(0.5) * (s.lb + s.ub);
-              tl = tu = kThr0;
-            } else {
-              tl = kThr0;
-              v = s.lb + kThr0;
-              tu = s.ub - v;
-            }
-          } else if (tu < kThr0) {
-            tu = kThr0;
-            v = s.ub - kThr0;
-            tl = v - s.lb;
-          }
-        } else if (s.ml != real(0.0)) {
-          if (tl < kThr0) {
-            tl = kThr0;
-            v = s.lb + kThr0;
-          }
-        } else if (tu < kThr0) {
-          tu = kThr0;
-          v = s.ub - kThr0;
-        }
-        bb.tl = s.ml != real(0.0) ? tl : real(1.0);
-        bb.tu = s.mu != real(0.0) ? tu : real(1.0);
-        bb.ll = s.ml != real(0.0) ? a.mu0 / tl : real(0.0);
-        bb.lu = s.mu != real(0.0) ? a.mu0 / tu : real(0.0);
-      }
-      ncl += s.ml + s.mu;
-      if constexpr (SOFT) {
-        SoftSt ss;
-        ncl += soft_init(s, si, v, a.mu0, bb, ss);
-        if (lane < kMaxDim) {
-          real* sp = SoftView{a.soft, N, nx, nu, c.oq()}.st(k, 0);
-          store_soft(sp, lane, ss);
-          store_sstep(sp, lane, SoftStep{0, 0, 0, 0, 0, 0});
-        }
-      }
-      if (lane < kMaxDim) store_bar(stk, 0, lane, bb);
-      if (uel) c.u()[(size_t)k * nu + lane] = v;
-      ui = uel ? v : real(0.0);
+    const real nc = gsum(lane < kMaxDim ? ncl : real(0.0));
+    if (lane == 0) {
+      qs[kQsAlphaP] = real(0.0);
+      qs[kQsAlphaD] = real(0.0);
+      qs[kQsLastAmin] = real(1.0);
+      qs[kQsSigmaMu] = real(0.0);
+      qs[kQsStatus] = -real(1.0);
+      qs[kQsIter] = real(0.0);
+      qs[kQsNc] = nc;
+      qs[kQsForceLq] = a.lq_fact == 2 ? real(1.0) : real(0.0);
+      qs[kQsLqRedo] = real(0.0);
     }
-    // x_k
-    {
-      real v;
-      if (k == 0) {
-        v = xel ? c.x0()[li] : real(0.0);
-      } else {
-        v = (a.warm_start && xel) ? c.x()[(size_t)k * nx + li] : real(0.0);
-      }
-      const Side s = c.side_x(k, lane);
-      Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
-      [[maybe_unused]] SoftIn si{0, 0, 0, 0, 0, 0, 0};
-      if constexpr (SOFT) si = SoftView{a.soft, N, nx, nu, c.oq()}.in_x(k, lane);
-      if (si.on == real(0.0) && (s.ml != real(0.0) || s.mu != real(0.0))) {
-        real tl = v - s.lb, tu = s.ub - v;
-        if (s.ml != real(0.0) && s.mu != real(0.0)) {
-          if (tl < kThr0) {
-            if (tu < kThr0) {
-              v = real(0.5) * (s.lb + s.ub);
-              tl = tu = kThr0;
-            } else {
-              tl = kThr0;
-              v = s.lb + kThr0;
-              tu = s.ub - v;
-            }
-          } else if (tu < kThr0) {
-            tu = kThr0;
-            v = s.ub - kThr0;
-            tl = v - s.lb;
-          }
-        } else if (s.ml != real(0.0)) {
-          if (tl < kThr0) {
-            tl = kThr0;
-            v = s.lb + kThr0;
-          }
-        } else if (tu < kThr0) {
-          tu = kThr0;
-          v = s.ub - kThr0;
-        }
-        bb.tl = s.ml != real(0.0) ? tl : real(1.0);
-        bb.tu = s.mu != real(0.0) ? tu : real(1.0);
-        bb.ll = s.ml != real(0.0) ? a.mu0 / tl : real(0.0);
-        bb.lu = s.mu != real(0.0) ? a.mu0 / tu : real(0.0);
-      }
-      ncl += s.ml + s.mu;
-      if constexpr (SOFT) {
-        SoftSt ss;
-        ncl += soft_init(s, si, v, a.mu0, bb, ss);
-        if (lane < kMaxDim) {
-          const SoftView sv{a.soft, N, nx, nu, c.oq()};
-          store_soft(sv.st(k, 1), lane, ss);
-          store_sstep(sv.st(k, 1), lane, SoftStep{0, 0, 0, 0, 0, 0});
-          if (k == N) {  // (no u_N: its rows hold the defaults)
-            store_soft(sv.st(N, 0), lane, SoftSt{0, 0, 1, 1, 0, 0});
-            store_sstep(sv.st(N, 0), lane, SoftStep{0, 0, 0, 0, 0, 0});
-          }
-        }
-      }
-      if (lane < kMaxDim) store_bar(stk, 1, lane, bb);
-      if (xel) {
-        c.x()[(size_t)k * nx + lane] = v;
-        c.pi()[(size_t)k * nx + lane] = real(0.0);
-      }
-      xi = xel ? v : real(0.0);
-    }
-    // general rows: t = max(v - lg, thr0), max(ug - v, thr0) at the initial
-    // x_k / u_k (no projection possible), lam = mu0 / t
-    if constexpr (GEN) {
-      real bxi[12], bui[12];
-      gather12(xi, bxi);
-      gather12(ui, bui);
-      for (int ch = 0; ch < c.nch; ++ch) {
-        const real v = c.g_row_dot(k, ch, lane, bxi, bui);
-        const Side s = c.side_g(k, ch, lane);
-        Bar bb{real(0.0), real(0.0), real(1.0), real(1.0)};
-        if (s.ml != real(0.0)) {
-          bb.tl = fmax(v - s.lb, kThr0);
-          bb.ll = a.mu0 / bb.tl;
-        }
-        if (s.mu != real(0.0)) {
-          bb.tu = fmax(s.ub - v, kThr0);
-          bb.lu = a.mu0 / bb.tu;
-        }
-        ncl += s.ml + s.mu;
-        if (lane < kMaxDim) {
-          real* g = c.gs(k, ch);
-          store_gbar(g, lane, bb);
-          store_gstep(g, lane, BarStep{0, 0, 0, 0});
-          g[kGenVal + lane] = v;
-        }
-      }
-    }
-    if (lane < kMaxDim) {
-      // zero step: the first RU pass applies nothing
-      stk[kStStep + lane] = real(0.0);
-      stk[kStStep + 12 + lane] = real(0.0);
-      stk[kStStep + 24 + lane] = real(0.0);
-      store_bstep(stk, 0, lane, BarStep{0, 0, 0, 0});
-      store_bstep(stk, 1, lane, BarStep{0, 0, 0, 0});
-    }
-  }
-  const real nc = gsum(lane < kMaxDim ? ncl : real(0.0));
-  if (lane == 0) {
-    qs[kQsAlphaP] = real(0.0);
-    qs[kQsAlphaD] = real(0.0);
-    qs[kQsLastAmin] = real(1.0);
-    qs[kQsSigmaMu] = real(0.0);
-    qs[kQsStatus] = -real(1.0);
-    qs[kQsIter] = real(0.0);
-    qs[kQsNc] = nc;
-    qs[kQsForceLq] = a.lq_fact == 2 ? real(1.0) : real(0.0);
-    qs[kQsLqRedo] = real(0.0);
-  }
-
     return;
   }
   const real nc = qs[kQsNc];
@@ -1107,121 +695,121 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
     const real res_comp = qs[kQsResComp], obj = qs[kQsObj];
     if (status < 0) status = 1;  // not reached: the last RB sweep always decides
     const int par = iter & 1;
-  // =================== outputs ===================
-  // Riccati factors of the last completed iteration (HPIPM's getters); the
-  // exiting sweep's own factorization is used only when no step was taken.
-  const int out_par = iter > 0 ? (par ^ 1) : par;
-  // pi_0 := Q0 x0 + S0'u0 + q0 + A0'(pi_1 + P_1 res_b0): the value of the
-  // stage-0 rebuild (ocp_qp_ipm_solver.cpp:347-373) with p_1 = pi_1 - P_1 x_1.
-  {
-    const real* st0 = c.st(0);
-    const real* st1 = c.st(1) + out_par * kRecSize;
-    real bx0[12], bu0[12];
-    gather12(xel ? c.x()[li] : real(0.0), bx0);
-    gather12(uel ? c.u()[li] : real(0.0), bu0);
-    real t = rec_P_mul(st1, lane < kMaxDim ? st0[kStRes + 24 + lane] : real(0.0),
-                       xel ? c.pi()[(size_t)nx + lane] : real(0.0));
-    if (!xel) t = real(0.0);
-    real bt[12];
-    gather12(t, bt);
-    real Qc[12], Sc[12], Ac[12];
-    c.col(c.Q(), nx, col, xel, Qc);
-    c.col(c.S(), nu, col, xel, Sc);
-    c.col(c.A(), nx, col, xel, Ac);
-    real p0 = c.el(c.q(), nx, li);
-    sfor<0, 12>([&](auto j) {
-      constexpr int J = decltype(j)::value;
-      p0 = fmadd(Qc[J], bx0[J], p0);
-      p0 = fmadd(Sc[J], bu0[J], p0);
-      p0 = fmadd(Ac[J], bt[J], p0);
-    });
-    if (xel) c.pi()[lane] = p0;
-  }
-  if (a.P || a.p || a.K || a.k) {
-    // Riccati matrices of the last factorization (HPIPM's get_ric_* getters),
-    // vectors by consistency: p_k = pi_k - P_k x_k, k_k = u_k - K_k x_k.
-    const size_t nxx = (size_t)nx * nx, nxu = (size_t)nx * nu;
-    for (int k = 0; k <= N; ++k) {
-      const real* stk = c.st(k) + out_par * kRecSize;
-      real bxk[12];
-      gather12(xel ? c.x()[(size_t)k * nx + li] : real(0.0), bxk);
-      real Pc[12];
-      if constexpr (kRecFactor) {  // P = Lp Lp': column l = sum_K Lp[:, K] Lp[l][K]
-        real Lr[12];
-        load_packed_lrow_d(stk + kRecP, col, Lr);
-        sfor<0, 12>([&](auto i) { Pc[decltype(i)::value] = real(0.0); });
-        tmul_acc(Lr, Lr, Pc);
-      } else {
-        load_packed_sym(stk + kRecP, col, Pc);
-      }
-      if (a.P && xel)
-        sfor<0, 12>([&](auto i) {
-          constexpr int I = decltype(i)::value;
-          if (I < nx) a.P[((size_t)qp * (N + 1) + k) * nxx + (size_t)lane * nx + I] = Pc[I];
-        });
-      if (a.p) {
-        const real px = rec_P_mul(stk, xel ? c.x()[(size_t)k * nx + li] : real(0.0), real(0.0));
-        if (xel) a.p[((size_t)qp * (N + 1) + k) * nx + lane] = c.pi()[(size_t)k * nx + lane] - px;
-      }
-      if (k < N) {
-        real Kc[12];
-        load12(stk + kRecK + col * 12, Kc);
-        if (a.K && xel)
+    // =================== outputs ===================
+    // Riccati factors of the last completed iteration (HPIPM's getters); the
+    // exiting sweep's own factorization is used only when no step was taken.
+    const int out_par = iter > 0 ? (par ^ 1) : par;
+    // pi_0 := Q0 x0 + S0'u0 + q0 + A0'(pi_1 + P_1 res_b0): the value of the
+    // stage-0 rebuild (ocp_qp_ipm_solver.cpp:347-373) with p_1 = pi_1 - P_1 x_1.
+    {
+      const real* st0 = c.st(0);
+      const real* st1 = c.st(1) + out_par * kRecSize;
+      real bx0[12], bu0[12];
+      gather12(xel ? c.x()[li] : real(0.0), bx0);
+      gather12(uel ? c.u()[li] : real(0.0), bu0);
+      real t = rec_P_mul(st1, lane < kMaxDim ? st0[kStRes + 24 + lane] : real(0.0),
+                         xel ? c.pi()[(size_t)nx + lane] : real(0.0));
+      if (!xel) t = real(0.0);
+      real bt[12];
+      gather12(t, bt);
+      real Qc[12], Sc[12], Ac[12];
+      c.col(c.Q(), nx, col, xel, Qc);
+      c.col(c.S(), nu, col, xel, Sc);
+      c.col(c.A(), nx, col, xel, Ac);
+      real p0 = c.el(c.q(), nx, li);
+      sfor<0, 12>([&](auto j) {
+        constexpr int J = decltype(j)::value;
+        p0 = fmadd(Qc[J], bx0[J], p0);
+        p0 = fmadd(Sc[J], bu0[J], p0);
+        p0 = fmadd(Ac[J], bt[J], p0);
+      });
+      if (xel) c.pi()[lane] = p0;
+    }
+    if (a.P || a.p || a.K || a.k) {
+      // Riccati matrices of the last factorization (HPIPM's get_ric_* getters),
+      // vectors by consistency: p_k = pi_k - P_k x_k, k_k = u_k - K_k x_k.
+      const size_t nxx = (size_t)nx * nx, nxu = (size_t)nx * nu;
+      for (int k = 0; k <= N; ++k) {
+        const real* stk = c.st(k) + out_par * kRecSize;
+        real bxk[12];
+        gather12(xel ? c.x()[(size_t)k * nx + li] : real(0.0), bxk);
+        real Pc[12];
+        if constexpr (kRecFactor) {  // P = Lp Lp': column l = sum_K Lp[:, K] Lp[l][K]
+          real Lr[12];
+          load_packed_lrow_d(stk + kRecP, col, Lr);
+          sfor<0, 12>([&](auto i) { Pc[decltype(i)::value] = real(0.0); });
+          tmul_acc(Lr, Lr, Pc);
+        } else {
+          load_packed_sym(stk + kRecP, col, Pc);
+        }
+        if (a.P && xel)
           sfor<0, 12>([&](auto i) {
             constexpr int I = decltype(i)::value;
-            if (I < nu) a.K[((size_t)qp * N + k) * nxu + (size_t)lane * nu + I] = Kc[I];
+            if (I < nx) a.P[((size_t)qp * (N + 1) + k) * nxx + (size_t)lane * nx + I] = Pc[I];
           });
-        if (a.k) {
-          real Kr[12];
-          sfor<0, 12>([&](auto j) {
-            constexpr int J = decltype(j)::value;
-            Kr[J] = stk[kRecK + J * 12 + li];
-          });
-          real kx = real(0.0);
-          sfor<0, 12>([&](auto j) {
-            constexpr int J = decltype(j)::value;
-            kx = fmadd(Kr[J], bxk[J], kx);
-          });
-          if (uel) a.k[((size_t)qp * N + k) * nu + lane] = c.u()[(size_t)k * nu + lane] - kx;
+        if (a.p) {
+          const real px = rec_P_mul(stk, xel ? c.x()[(size_t)k * nx + li] : real(0.0), real(0.0));
+          if (xel) a.p[((size_t)qp * (N + 1) + k) * nx + lane] = c.pi()[(size_t)k * nx + lane] - px;
+        }
+        if (k < N) {
+          real Kc[12];
+          load12(stk + kRecK + col * 12, Kc);
+          if (a.K && xel)
+            sfor<0, 12>([&](auto i) {
+              constexpr int I = decltype(i)::value;
+              if (I < nu) a.K[((size_t)qp * N + k) * nxu + (size_t)lane * nu + I] = Kc[I];
+            });
+          if (a.k) {
+            real Kr[12];
+            sfor<0, 12>([&](auto j) {
+              constexpr int J = decltype(j)::value;
+              Kr[J] = stk[kRecK + J * 12 + li];
+            });
+            real kx = real(0.0);
+            sfor<0, 12>([&](auto j) {
+              constexpr int J = decltype(j)::value;
+              kx = fmadd(Kr[J], bxk[J], kx);
+            });
+            if (uel) a.k[((size_t)qp * N + k) * nu + lane] = c.u()[(size_t)k * nu + lane] - kx;
+          }
         }
       }
     }
-  }
-  if constexpr (SOFT) {
-    // the slacks (0 where the variable is not soft or the side is masked)
-    const SoftView sv{a.soft, N, nx, nu, c.oq()};
-    for (int k = 0; k <= N; ++k) {
-      if (k < N && uel) {
-        const Side s = c.side_u(k, lane);
-        const SoftIn si = sv.in_u(k, lane);
-        const SoftSt ss = load_soft(sv.st(k, 0), lane);
-        const bool on = si.on != real(0.0);
-        const size_t o = ((size_t)qp * N + k) * nu + lane;
-        if (a.soft.sl_u) a.soft.sl_u[o] = on && s.ml != real(0.0) ? ss.sl : real(0.0);
-        if (a.soft.su_u) a.soft.su_u[o] = on && s.mu != real(0.0) ? ss.su : real(0.0);
-      }
-      if (xel) {
-        const Side s = c.side_x(k, lane);
-        const SoftIn si = sv.in_x(k, lane);
-        const SoftSt ss = load_soft(sv.st(k, 1), lane);
-        const bool on = si.on != real(0.0);
-        const size_t o = ((size_t)qp * (N + 1) + k) * nx + lane;
-        if (a.soft.sl_x) a.soft.sl_x[o] = on && s.ml != real(0.0) ? ss.sl : real(0.0);
-        if (a.soft.su_x) a.soft.su_x[o] = on && s.mu != real(0.0) ? ss.su : real(0.0);
+    if constexpr (SOFT) {
+      // the slacks (0 where the variable is not soft or the side is masked)
+      const SoftView sv{a.soft, N, nx, nu, c.oq()};
+      for (int k = 0; k <= N; ++k) {
+        if (k < N && uel) {
+          const Side s = c.side_u(k, lane);
+          const SoftIn si = sv.in_u(k, lane);
+          const SoftSt ss = load_soft(sv.st(k, 0), lane);
+          const bool on = si.on != real(0.0);
+          const size_t o = ((size_t)qp * N + k) * nu + lane;
+          if (a.soft.sl_u) a.soft.sl_u[o] = on && s.ml != real(0.0) ? ss.sl : real(0.0);
+          if (a.soft.su_u) a.soft.su_u[o] = on && s.mu != real(0.0) ? ss.su : real(0.0);
+        }
+        if (xel) {
+          const Side s = c.side_x(k, lane);
+          const SoftIn si = sv.in_x(k, lane);
+          const SoftSt ss = load_soft(sv.st(k, 1), lane);
+          const bool on = si.on != real(0.0);
+          const size_t o = ((size_t)qp * (N + 1) + k) * nx + lane;
+          if (a.soft.sl_x) a.soft.sl_x[o] = on && s.ml != real(0.0) ? ss.sl : real(0.0);
+          if (a.soft.su_x) a.soft.su_x[o] = on && s.mu != real(0.0) ? ss.su : real(0.0);
+        }
       }
     }
-  }
-  if (lane == 0) {
-    if (a.status) a.status[qp] = status;
-    if (a.iter) a.iter[qp] = nc > real(0.0) ? iter : 0;
-    if (a.res) {
-      a.res[(size_t)qp * 4 + 0] = res_stat;
-      a.res[(size_t)qp * 4 + 1] = res_eq;
-      a.res[(size_t)qp * 4 + 2] = res_ineq;
-      a.res[(size_t)qp * 4 + 3] = res_comp;
+    if (lane == 0) {
+      if (a.status) a.status[qp] = status;
+      if (a.iter) a.iter[qp] = nc > real(0.0) ? iter : 0;
+      if (a.res) {
+        a.res[(size_t)qp * 4 + 0] = res_stat;
+        a.res[(size_t)qp * 4 + 1] = res_eq;
+        a.res[(size_t)qp * 4 + 2] = res_ineq;
+        a.res[(size_t)qp * 4 + 3] = res_comp;
+      }
+      if (a.obj) a.obj[qp] = obj;
     }
-    if (a.obj) a.obj[qp] = obj;
-  }
     return;
   }
   if (status >= 0) return;  // this QP has exited
@@ -1764,7 +1352,6 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
       qs[kQsObj] = obj;
       qs[kQsStatus] = (real)status;
     }
-
     return;
   }
   if constexpr (PH == kPhIR || PH == kPhIRP || PH == kPhIS || PH == kPhF3 || PH == kPhLqChk) {
@@ -2103,125 +1690,124 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
   const real mu = qs[kQsMu], musum_all = qs[kQsMuSum];
   real sigma_mu = qs[kQsSigmaMu];
   if constexpr (PH == kPhB2) {
-        // ---- B2: corrector vectors (element-owned recursion) ----
-        real pnext = real(0.0);  // p_{k+1}, element-owned
-        {
-          real* stN = c.st(N);
-          const Side sx = c.side_x(N, lane);
-          const real xv = xel && c.has_bars(1) ? c.x()[(size_t)N * nx + lane] : real(0.0);
-          real G = real(0.0), g = real(0.0);
-          if (lane < kMaxDim) {
-            const BarStep dx = c.bstep(stN, 1, lane);
-            if constexpr (SOFT) {
-              const SoftView sv{a.soft, N, nx, nu, c.oq()};
-              const SoftStep ex = load_sstep(sv.st(N, 1), lane);
-              gamma_soft(sx, c.bar(stN, 1, lane), sv.in_x(N, lane), load_soft(sv.st(N, 1), lane), xv,
-                         dx.dll * dx.dtl, dx.dlu * dx.dtu, ex.dll * ex.dtl, ex.dlu * ex.dtu, sigma_mu, G, g);
-            } else {
-            gamma_of(sx, c.bar(stN, 1, lane), xv, dx.dll * dx.dtl, dx.dlu * dx.dtu, sigma_mu, G, g);
-            }
-          }
-          pnext = lane < kMaxDim && xel ? stN[kStRes + 12 + lane] + g : real(0.0);
-          if constexpr (GEN == 2) {
-            // (C = NULL: the terminal stage has no general-row gradient, D_N is absent)
-            real ra, qa;
-            g_grad(N, true, sigma_mu, ra, qa);
-            if (lane < kMaxDim && xel) pnext += qa;
-          }
-          if (lane < kMaxDim) stN[par * kRecSize + kRecPv + lane] = pnext;
+    // ---- B2: corrector vectors (element-owned recursion) ----
+    real pnext = real(0.0);  // p_{k+1}, element-owned
+    {
+      real* stN = c.st(N);
+      const Side sx = c.side_x(N, lane);
+      const real xv = xel && c.has_bars(1) ? c.x()[(size_t)N * nx + lane] : real(0.0);
+      real G = real(0.0), g = real(0.0);
+      if (lane < kMaxDim) {
+        const BarStep dx = c.bstep(stN, 1, lane);
+        if constexpr (SOFT) {
+          const SoftView sv{a.soft, N, nx, nu, c.oq()};
+          const SoftStep ex = load_sstep(sv.st(N, 1), lane);
+          gamma_soft(sx, c.bar(stN, 1, lane), sv.in_x(N, lane), load_soft(sv.st(N, 1), lane), xv,
+                     dx.dll * dx.dtl, dx.dlu * dx.dtu, ex.dll * ex.dtl, ex.dlu * ex.dtu, sigma_mu, G, g);
+        } else {
+          gamma_of(sx, c.bar(stN, 1, lane), xv, dx.dll * dx.dtl, dx.dlu * dx.dtu, sigma_mu, G, g);
         }
-        for (int k = N - 1; k >= 0; --k) {
-          tstamp(40);
-          real* stk = c.st(k);
-          real* rec = stk + par * kRecSize;
-          [[maybe_unused]] const real* recn = c.st(k + 1) + par * kRecSize;
-          // the stage's element-owned loads, all issued before any is waited for (valid
-          // addresses on every lane, masked after; a load under a lane condition would be a
-          // branch that waits for it)
-          const Side su = c.side_u(k, lane), sx = c.side_x(k, lane);
-          const int iu = li < nu ? li : 0, ix = li < nx ? li : 0;
-          const real u_ld = c.u()[(size_t)k * nu + iu], x_ld = c.x()[(size_t)k * nx + ix];
-          const Bar bu = c.bar(stk, 0, li), bx = c.bar(stk, 1, li);
-          const BarStep du = c.bstep(stk, 0, li), dx = c.bstep(stk, 1, li);
-          const real r_ld = stk[kStRes + li], q_ld = stk[kStRes + 12 + li], b_ld = stk[kStRes + 24 + li];
-          real gv_ld = real(0.0);
-          if constexpr (GEN == 1) {
-            // D'gamma_corr = D'gamma_pred + sigma mu D'e + D'z (gamma is affine in both)
-            const real* v = c.gv(k);
-            gv_ld = v[li] + v[24 + li] + sigma_mu * v[12 + li];
-          }
-          // x, u enter only through the barrier terms of the bound families present
-          const real uv = uel && c.has_bars(0) ? u_ld : real(0.0);
-          const real xv = xel && c.has_bars(1) ? x_ld : real(0.0);
-          real Gu = real(0.0), gu = real(0.0), Gx = real(0.0), gx = real(0.0);
-          if constexpr (SOFT) {
-            if (lane < kMaxDim) {
-              const SoftView sv{a.soft, N, nx, nu, c.oq()};
-              const SoftStep eu = load_sstep(sv.st(k, 0), lane), ex = load_sstep(sv.st(k, 1), lane);
-              gamma_soft(su, bu, sv.in_u(k, lane), load_soft(sv.st(k, 0), lane), uv, du.dll * du.dtl,
-                         du.dlu * du.dtu, eu.dll * eu.dtl, eu.dlu * eu.dtu, sigma_mu, Gu, gu);
-              gamma_soft(sx, bx, sv.in_x(k, lane), load_soft(sv.st(k, 1), lane), xv, dx.dll * dx.dtl,
-                         dx.dlu * dx.dtu, ex.dll * ex.dtl, ex.dlu * ex.dtu, sigma_mu, Gx, gx);
-            }
-          } else
-          if (lane < kMaxDim) {
-            gamma_of(su, bu, uv, du.dll * du.dtl, du.dlu * du.dtu, sigma_mu, Gu, gu);
-            gamma_of(sx, bx, xv, dx.dll * dx.dtl, dx.dlu * dx.dtu, sigma_mu, Gx, gx);
-          }
-          real rt = lane < kMaxDim && uel ? r_ld + gu : real(0.0);
-          real qt = lane < kMaxDim && xel ? q_ld + gx : real(0.0);
-          if constexpr (GEN == 1) {
-            if (lane < kMaxDim && uel) rt += gv_ld;
-          } else if constexpr (GEN) {
-            real ra, qa;
-            g_grad(k, true, sigma_mu, ra, qa);
-            if (lane < kMaxDim && uel) rt += ra;
-            if (lane < kMaxDim && xel) qt += qa;
-          }
-          [[maybe_unused]] const real bt = lane < kMaxDim ? b_ld : real(0.0);
-          // w = P_{k+1} b~ + p_{k+1} (P_{k+1} b~ from RB, classical Riccati)
-          real w;
-          if constexpr (kRecPbOn<SQRT>) {
-            w = rec[kRecPb + li] + pnext;
-          } else {
-            w = rec_P_mul(recn, bt, pnext);
-          }
-          // g = r~ + B'w ; f = q~ + A'w
-          real Bc[12], Ac[12];
-          c.col(c.B() + (size_t)k * c.nxu(), nx, col, uel, Bc);
-          c.col(c.A() + (size_t)k * c.nxx(), nx, col, xel, Ac);
-          real g = rt, f = qt;
-          dot_bcast2(Bc, Ac, w, g, f);
-          if (lane >= kMaxDim) g = real(0.0);
-          // p = f + K'g  (K column-owned: lane j holds K[:, j])
-          real Kc[12];
-          load12(rec + kRecK + col * 12, Kc);
-          const real pv = dot_bcast(Kc, g, f);
-          // y = L^-1 g (row-owned L), then z = L^-T y (column-owned L), k = -z
-          real Lr[12], Lc[12];
-          load_packed_lrow(rec + kRecL, li, Lr);
-          load_packed_lcol(rec + kRecL, col, Lc);
-          const real rs = rec[kRecRs + li];
-          real y = g;
-          sfor<0, 12>([&](auto kk) {
-            constexpr int K = decltype(kk)::value;
-            const real yk = bc<K>(apply_rs(y, rs));
-            if (lane == K) y = yk;
-            if (lane > K) y = fmadd(-Lr[K], yk, y);
-          });
-          sfor_down<0, 12>([&](auto kk) {
-            constexpr int K = decltype(kk)::value;
-            const real zk = bc<K>(apply_rs(y, rs));
-            if (lane == K) y = zk;
-            if (lane < K) y = fmadd(-Lc[K], zk, y);
-          });
-          const real kv = lane < kMaxDim && uel ? -y : real(0.0);
-          if (lane < kMaxDim) {
-            rec[kRecKv + lane] = kv;
-            rec[kRecPv + lane] = xel ? pv : real(0.0);
-          }
-          pnext = xel ? pv : real(0.0);
+      }
+      pnext = lane < kMaxDim && xel ? stN[kStRes + 12 + lane] + g : real(0.0);
+      if constexpr (GEN == 2) {
+        // (C = NULL: the terminal stage has no general-row gradient, D_N is absent)
+        real ra, qa;
+        g_grad(N, true, sigma_mu, ra, qa);
+        if (lane < kMaxDim && xel) pnext += qa;
+      }
+      if (lane < kMaxDim) stN[par * kRecSize + kRecPv + lane] = pnext;
+    }
+    for (int k = N - 1; k >= 0; --k) {
+      tstamp(40);
+      real* stk = c.st(k);
+      real* rec = stk + par * kRecSize;
+      [[maybe_unused]] const real* recn = c.st(k + 1) + par * kRecSize;
+      // the stage's element-owned loads, all issued before any is waited for (valid
+      // addresses on every lane, masked after; a load under a lane condition would be a
+      // branch that waits for it)
+      const Side su = c.side_u(k, lane), sx = c.side_x(k, lane);
+      const int iu = li < nu ? li : 0, ix = li < nx ? li : 0;
+      const real u_ld = c.u()[(size_t)k * nu + iu], x_ld = c.x()[(size_t)k * nx + ix];
+      const Bar bu = c.bar(stk, 0, li), bx = c.bar(stk, 1, li);
+      const BarStep du = c.bstep(stk, 0, li), dx = c.bstep(stk, 1, li);
+      const real r_ld = stk[kStRes + li], q_ld = stk[kStRes + 12 + li], b_ld = stk[kStRes + 24 + li];
+      real gv_ld = real(0.0);
+      if constexpr (GEN == 1) {
+        // D'gamma_corr = D'gamma_pred + sigma mu D'e + D'z (gamma is affine in both)
+        const real* v = c.gv(k);
+        gv_ld = v[li] + v[24 + li] + sigma_mu * v[12 + li];
+      }
+      // x, u enter only through the barrier terms of the bound families present
+      const real uv = uel && c.has_bars(0) ? u_ld : real(0.0);
+      const real xv = xel && c.has_bars(1) ? x_ld : real(0.0);
+      real Gu = real(0.0), gu = real(0.0), Gx = real(0.0), gx = real(0.0);
+      if constexpr (SOFT) {
+        if (lane < kMaxDim) {
+          const SoftView sv{a.soft, N, nx, nu, c.oq()};
+          const SoftStep eu = load_sstep(sv.st(k, 0), lane), ex = load_sstep(sv.st(k, 1), lane);
+          gamma_soft(su, bu, sv.in_u(k, lane), load_soft(sv.st(k, 0), lane), uv, du.dll * du.dtl,
+                     du.dlu * du.dtu, eu.dll * eu.dtl, eu.dlu * eu.dtu, sigma_mu, Gu, gu);
+          gamma_soft(sx, bx, sv.in_x(k, lane), load_soft(sv.st(k, 1), lane), xv, dx.dll * dx.dtl,
+                     dx.dlu * dx.dtu, ex.dll * ex.dtl, ex.dlu * ex.dtu, sigma_mu, Gx, gx);
         }
+      } else if (lane < kMaxDim) {
+        gamma_of(su, bu, uv, du.dll * du.dtl, du.dlu * du.dtu, sigma_mu, Gu, gu);
+        gamma_of(sx, bx, xv, dx.dll * dx.dtl, dx.dlu * dx.dtu, sigma_mu, Gx, gx);
+      }
+      real rt = lane < kMaxDim && uel ? r_ld + gu : real(0.0);
+      real qt = lane < kMaxDim && xel ? q_ld + gx : real(0.0);
+      if constexpr (GEN == 1) {
+        if (lane < kMaxDim && uel) rt += gv_ld;
+      } else if constexpr (GEN) {
+        real ra, qa;
+        g_grad(k, true, sigma_mu, ra, qa);
+        if (lane < kMaxDim && uel) rt += ra;
+        if (lane < kMaxDim && xel) qt += qa;
+      }
+      [[maybe_unused]] const real bt = lane < kMaxDim ? b_ld : real(0.0);
+      // w = P_{k+1} b~ + p_{k+1} (P_{k+1} b~ from RB, classical Riccati)
+      real w;
+      if constexpr (kRecPbOn<SQRT>) {
+        w = rec[kRecPb + li] + pnext;
+      } else {
+        w = rec_P_mul(recn, bt, pnext);
+      }
+      // g = r~ + B'w ; f = q~ + A'w
+      real Bc[12], Ac[12];
+      c.col(c.B() + (size_t)k * c.nxu(), nx, col, uel, Bc);
+      c.col(c.A() + (size_t)k * c.nxx(), nx, col, xel, Ac);
+      real g = rt, f = qt;
+      dot_bcast2(Bc, Ac, w, g, f);
+      if (lane >= kMaxDim) g = real(0.0);
+      // p = f + K'g  (K column-owned: lane j holds K[:, j])
+      real Kc[12];
+      load12(rec + kRecK + col * 12, Kc);
+      const real pv = dot_bcast(Kc, g, f);
+      // y = L^-1 g (row-owned L), then z = L^-T y (column-owned L), k = -z
+      real Lr[12], Lc[12];
+      load_packed_lrow(rec + kRecL, li, Lr);
+      load_packed_lcol(rec + kRecL, col, Lc);
+      const real rs = rec[kRecRs + li];
+      real y = g;
+      sfor<0, 12>([&](auto kk) {
+        constexpr int K = decltype(kk)::value;
+        const real yk = bc<K>(apply_rs(y, rs));
+        if (lane == K) y = yk;
+        if (lane > K) y = fmadd(-Lr[K], yk, y);
+      });
+      sfor_down<0, 12>([&](auto kk) {
+        constexpr int K = decltype(kk)::value;
+        const real zk = bc<K>(apply_rs(y, rs));
+        if (lane == K) y = zk;
+        if (lane < K) y = fmadd(-Lc[K], zk, y);
+      });
+      const real kv = lane < kMaxDim && uel ? -y : real(0.0);
+      if (lane < kMaxDim) {
+        rec[kRecKv + lane] = kv;
+        rec[kRecPv + lane] = xel ? pv : real(0.0);
+      }
+      pnext = xel ? pv : real(0.0);
+    }
     return;
   }
   if constexpr (PH == kPhF1 || PH == kPhF2) {
@@ -2236,156 +1822,156 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
     const bool final_step = corr || !a.pred_corr;
     const bool lq_chk = !corr && a.lq_fact == 1 && !a.lq_redo && qs[kQsForceLq] == real(0.0);
     const bool keep_step = final_step || lq_chk;
-      // ---- forward step (F1 predictor / F2 corrector), row-owned ----
-      ap = real(1e30);
-      ad = real(1e30);
-      real dxk = real(0.0);  // dx_0 = 0 (x0 fixed)
-      for (int k = 0; k <= N; ++k) {
-        tstamp(corr ? 31 : 30);
-        real* stk = c.st(k);
-        const real* rec = stk + par * kRecSize;
-        // dpi = P dx + p is part of the final step only (F2, or F1 without corrector)
-        real dpi = real(0.0);
-        if (keep_step) dpi = rec_P_mul(rec, dxk, rec[kRecPv + li]);
-        real du = real(0.0), dxn = real(0.0);
-        if (k < N) {
-          // du = K dx + k, dx+ = A dx + B du + b~ (open loop: the QP's own A, B; b~ = res_b,
-          // unchanged between predictor and corrector)
-          real Kr[12], Ar[12];
-          sfor<0, 12>([&](auto j) {
-            constexpr int J = decltype(j)::value;
-            Kr[J] = rec[kRecK + J * 12 + li];
-          });
-          c.row(c.A() + (size_t)k * c.nxx(), nx, nx, li, xel, Ar);
-          du = rec[kRecKv + li];
-          dxn = stk[kStRes + 24 + li];
-          dot_bcast2(Kr, Ar, dxk, du, dxn);
-          if (!uel) du = real(0.0);
-          real Br[12];
-          c.row(c.B() + (size_t)k * c.nxu(), nx, nu, li, xel, Br);
-          dxn = dot_bcast(Br, du, dxn);
-        }
-        if (!uel || k == N) du = real(0.0);
-        if (!xel) {
-          dxn = real(0.0);
-          dpi = real(0.0);
-        }
-        if constexpr (GEN) {
-          // general rows: dv = C dx + D du, dt / dlam, step ratios
-          // (GEN == 1, F1: z_i = ml dlam_l dt_l / t_l - mu dlam_u dt_u / t_u and D'z, the
-          // predictor-product part of the corrector's D'gamma, for B2)
-          constexpr bool kZ = GEN == 1 && !corr;
-          real gza = real(0.0);
-          for (int ch = 0; ch < c.nch; ++ch) {
-            real* g = c.gs(k, ch);
-            real Cr[12], Dr[12];
-            c.g_row(k, ch, lane, Cr, Dr);
-            const real dv = dot_bcast(Dr, du, GEN == 2 ? dot_bcast(Cr, dxk, real(0.0)) : real(0.0));
-            real z = real(0.0);
-            if (lane < kMaxDim) {
-              const Side sg = c.side_g(k, ch, lane);
-              const Bar bg = load_gbar(g, lane);
-              real el = real(0.0), eu = real(0.0), sm = real(0.0);
-              if (corr) {
-                const BarStep pd = load_gstep(g, lane);
-                el = pd.dll * pd.dtl;
-                eu = pd.dlu * pd.dtu;
-                sm = sigma_mu;
-              }
-              const BarStep d = bar_step(sg, bg, g[kGenVal + lane], dv, el, eu, sm);
-              bad |= huge(d.dtl) || huge(d.dtu) || huge(d.dll) || huge(d.dlu);
-              ratio(sg, bg, d, ap, ad);
-              if (!corr) aff_sums(sg, bg, d, s1, s2);
-              store_gstep(g, lane, d);
-              if constexpr (kZ) {
-                if (sg.ml != real(0.0)) z += d.dll * d.dtl / bg.tl;
-                if (sg.mu != real(0.0)) z -= d.dlu * d.dtu / bg.tu;
-              }
+    // ---- forward step (F1 predictor / F2 corrector), row-owned ----
+    ap = real(1e30);
+    ad = real(1e30);
+    real dxk = real(0.0);  // dx_0 = 0 (x0 fixed)
+    for (int k = 0; k <= N; ++k) {
+      tstamp(corr ? 31 : 30);
+      real* stk = c.st(k);
+      const real* rec = stk + par * kRecSize;
+      // dpi = P dx + p is part of the final step only (F2, or F1 without corrector)
+      real dpi = real(0.0);
+      if (keep_step) dpi = rec_P_mul(rec, dxk, rec[kRecPv + li]);
+      real du = real(0.0), dxn = real(0.0);
+      if (k < N) {
+        // du = K dx + k, dx+ = A dx + B du + b~ (open loop: the QP's own A, B; b~ = res_b,
+        // unchanged between predictor and corrector)
+        real Kr[12], Ar[12];
+        sfor<0, 12>([&](auto j) {
+          constexpr int J = decltype(j)::value;
+          Kr[J] = rec[kRecK + J * 12 + li];
+        });
+        c.row(c.A() + (size_t)k * c.nxx(), nx, nx, li, xel, Ar);
+        du = rec[kRecKv + li];
+        dxn = stk[kStRes + 24 + li];
+        dot_bcast2(Kr, Ar, dxk, du, dxn);
+        if (!uel) du = real(0.0);
+        real Br[12];
+        c.row(c.B() + (size_t)k * c.nxu(), nx, nu, li, xel, Br);
+        dxn = dot_bcast(Br, du, dxn);
+      }
+      if (!uel || k == N) du = real(0.0);
+      if (!xel) {
+        dxn = real(0.0);
+        dpi = real(0.0);
+      }
+      if constexpr (GEN) {
+        // general rows: dv = C dx + D du, dt / dlam, step ratios
+        // (GEN == 1, F1: z_i = ml dlam_l dt_l / t_l - mu dlam_u dt_u / t_u and D'z, the
+        // predictor-product part of the corrector's D'gamma, for B2)
+        constexpr bool kZ = GEN == 1 && !corr;
+        real gza = real(0.0);
+        for (int ch = 0; ch < c.nch; ++ch) {
+          real* g = c.gs(k, ch);
+          real Cr[12], Dr[12];
+          c.g_row(k, ch, lane, Cr, Dr);
+          const real dv = dot_bcast(Dr, du, GEN == 2 ? dot_bcast(Cr, dxk, real(0.0)) : real(0.0));
+          real z = real(0.0);
+          if (lane < kMaxDim) {
+            const Side sg = c.side_g(k, ch, lane);
+            const Bar bg = load_gbar(g, lane);
+            real el = real(0.0), eu = real(0.0), sm = real(0.0);
+            if (corr) {
+              const BarStep pd = load_gstep(g, lane);
+              el = pd.dll * pd.dtl;
+              eu = pd.dlu * pd.dtu;
+              sm = sigma_mu;
             }
+            const BarStep d = bar_step(sg, bg, g[kGenVal + lane], dv, el, eu, sm);
+            bad |= huge(d.dtl) || huge(d.dtu) || huge(d.dll) || huge(d.dlu);
+            ratio(sg, bg, d, ap, ad);
+            if (!corr) aff_sums(sg, bg, d, s1, s2);
+            store_gstep(g, lane, d);
             if constexpr (kZ) {
-              // (D'z)_j = sum_i D[i][j] z_i: row i's products through this group's LDS
-              // block, summed down column j by lane j
-              real Y[12], M[12];
-              sfor<0, 12>([&](auto j) { Y[decltype(j)::value] = Dr[decltype(j)::value] * z; });
-              lds_put_col(f1_lds_grp, lane, Y);
-              lds_wave_fence();
-              lds_get_row(f1_lds_grp, li, M);
-              sfor<0, 12>([&](auto i) { gza += M[decltype(i)::value]; });
-              lds_wave_fence();
+              if (sg.ml != real(0.0)) z += d.dll * d.dtl / bg.tl;
+              if (sg.mu != real(0.0)) z -= d.dlu * d.dtu / bg.tu;
             }
           }
           if constexpr (kZ) {
-            if (lane < kMaxDim) c.gv(k)[24 + lane] = gza;
+            // (D'z)_j = sum_i D[i][j] z_i: row i's products through this group's LDS
+            // block, summed down column j by lane j
+            real Y[12], M[12];
+            sfor<0, 12>([&](auto j) { Y[decltype(j)::value] = Dr[decltype(j)::value] * z; });
+            lds_put_col(f1_lds_grp, lane, Y);
+            lds_wave_fence();
+            lds_get_row(f1_lds_grp, li, M);
+            sfor<0, 12>([&](auto i) { gza += M[decltype(i)::value]; });
+            lds_wave_fence();
           }
         }
-        if (lane < kMaxDim) {
-          const Side su = c.side_u(k, lane), sx = c.side_x(k, lane);
-          const Bar bu = c.bar(stk, 0, lane), bx = c.bar(stk, 1, lane);
-          const real uv = (uel && k < N && c.has_bars(0)) ? c.u()[(size_t)k * nu + lane] : real(0.0);
-          const real xv = xel && c.has_bars(1) ? c.x()[(size_t)k * nx + lane] : real(0.0);
-          real eul = real(0.0), euu = real(0.0), exl = real(0.0), exu = real(0.0), smu = real(0.0);
-          if (corr) {
-            const BarStep pu = c.bstep(stk, 0, lane), px = c.bstep(stk, 1, lane);
-            eul = pu.dll * pu.dtl;
-            euu = pu.dlu * pu.dtu;
-            exl = px.dll * px.dtl;
-            exu = px.dlu * px.dtu;
-            smu = sigma_mu;
-          }
-          BarStep nu_, nx_;
-          if constexpr (SOFT) {
-            const SoftView sv{a.soft, N, nx, nu, c.oq()};
-            real* const pu = sv.st(k, 0);
-            real* const px = sv.st(k, 1);
-            const SoftIn qu = sv.in_u(k, lane), qx = sv.in_x(k, lane);
-            const SoftSt ssu = load_soft(pu, lane), ssx = load_soft(px, lane);
-            real sul = real(0.0), suu = real(0.0), sxl = real(0.0), sxu = real(0.0);
-            if (corr) {
-              const SoftStep pe = load_sstep(pu, lane), qe = load_sstep(px, lane);
-              sul = pe.dll * pe.dtl;
-              suu = pe.dlu * pe.dtu;
-              sxl = qe.dll * qe.dtl;
-              sxu = qe.dlu * qe.dtu;
-            }
-            SoftStep eu_, ex_;
-            soft_step(su, bu, qu, ssu, uv, du, eul, euu, sul, suu, smu, nu_, eu_);
-            soft_step(sx, bx, qx, ssx, xv, dxk, exl, exu, sxl, sxu, smu, nx_, ex_);
-            ratio_soft(su, qu, ssu, eu_, ap, ad);
-            ratio_soft(sx, qx, ssx, ex_, ap, ad);
-            if (!corr) {
-              aff_soft(su, qu, ssu, eu_, s1, s2);
-              aff_soft(sx, qx, ssx, ex_, s1, s2);
-            }
-            store_sstep(pu, lane, eu_);
-            store_sstep(px, lane, ex_);
-            if (final_step) bad |= huge_soft(eu_) || huge_soft(ex_) || huge(nx_.dtl) || huge(nx_.dtu) ||
-                                   huge(nx_.dll) || huge(nx_.dlu);
-          } else {
-            nu_ = bar_step(su, bu, uv, du, eul, euu, smu);
-            nx_ = bar_step(sx, bx, xv, dxk, exl, exu, smu);
-          }
-          ratio(su, bu, nu_, ap, ad);
-          ratio(sx, bx, nx_, ap, ad);
-          if (!corr) {
-            aff_sums(su, bu, nu_, s1, s2);
-            aff_sums(sx, bx, nx_, s1, s2);
-          }
-          c.put_bstep(stk, 0, lane, nu_);
-          c.put_bstep(stk, 1, lane, nx_);
-          if (final_step)
-            bad |= huge(du) || huge(dxk) || huge(dpi) || huge(nu_.dtl) || huge(nu_.dtu) ||
-                   huge(nu_.dll) || huge(nu_.dlu);
-          if (keep_step) {  // (otherwise the predictor's du / dx / dpi are not used)
-            stk[kStStep + lane] = du;
-            stk[kStStep + 12 + lane] = dxk;
-            stk[kStStep + 24 + lane] = k > 0 ? dpi : real(0.0);
-          }
+        if constexpr (kZ) {
+          if (lane < kMaxDim) c.gv(k)[24 + lane] = gza;
         }
-        dxk = dxn;
       }
-    real* const next = a.stat && lane == 0
-                             ? a.stat + ((size_t)qp * a.stat_rows + iter + 1) * kStatCols
-                             : nullptr;  // HPIPM stores step kk in row kk+1
+      if (lane < kMaxDim) {
+        const Side su = c.side_u(k, lane), sx = c.side_x(k, lane);
+        const Bar bu = c.bar(stk, 0, lane), bx = c.bar(stk, 1, lane);
+        const real uv = (uel && k < N && c.has_bars(0)) ? c.u()[(size_t)k * nu + lane] : real(0.0);
+        const real xv = xel && c.has_bars(1) ? c.x()[(size_t)k * nx + lane] : real(0.0);
+        real eul = real(0.0), euu = real(0.0), exl = real(0.0), exu = real(0.0), smu = real(0.0);
+        if (corr) {
+          const BarStep pu = c.bstep(stk, 0, lane), px = c.bstep(stk, 1, lane);
+          eul = pu.dll * pu.dtl;
+          euu = pu.dlu * pu.dtu;
+          exl = px.dll * px.dtl;
+          exu = px.dlu * px.dtu;
+          smu = sigma_mu;
+        }
+        BarStep nu_, nx_;
+        if constexpr (SOFT) {
+          const SoftView sv{a.soft, N, nx, nu, c.oq()};
+          real* const pu = sv.st(k, 0);
+          real* const px = sv.st(k, 1);
+          const SoftIn qu = sv.in_u(k, lane), qx = sv.in_x(k, lane);
+          const SoftSt ssu = load_soft(pu, lane), ssx = load_soft(px, lane);
+          real sul = real(0.0), suu = real(0.0), sxl = real(0.0), sxu = real(0.0);
+          if (corr) {
+            const SoftStep pe = load_sstep(pu, lane), qe = load_sstep(px, lane);
+            sul = pe.dll * pe.dtl;
+            suu = pe.dlu * pe.dtu;
+            sxl = qe.dll * qe.dtl;
+            sxu = qe.dlu * qe.dtu;
+          }
+          SoftStep eu_, ex_;
+          soft_step(su, bu, qu, ssu, uv, du, eul, euu, sul, suu, smu, nu_, eu_);
+          soft_step(sx, bx, qx, ssx, xv, dxk, exl, exu, sxl, sxu, smu, nx_, ex_);
+          ratio_soft(su, qu, ssu, eu_, ap, ad);
+          ratio_soft(sx, qx, ssx, ex_, ap, ad);
+          if (!corr) {
+            aff_soft(su, qu, ssu, eu_, s1, s2);
+            aff_soft(sx, qx, ssx, ex_, s1, s2);
+          }
+          store_sstep(pu, lane, eu_);
+          store_sstep(px, lane, ex_);
+          if (final_step) bad |= huge_soft(eu_) || huge_soft(ex_) || huge(nx_.dtl) || huge(nx_.dtu) ||
+                                 huge(nx_.dll) || huge(nx_.dlu);
+        } else {
+          nu_ = bar_step(su, bu, uv, du, eul, euu, smu);
+          nx_ = bar_step(sx, bx, xv, dxk, exl, exu, smu);
+        }
+        ratio(su, bu, nu_, ap, ad);
+        ratio(sx, bx, nx_, ap, ad);
+        if (!corr) {
+          aff_sums(su, bu, nu_, s1, s2);
+          aff_sums(sx, bx, nx_, s1, s2);
+        }
+        c.put_bstep(stk, 0, lane, nu_);
+        c.put_bstep(stk, 1, lane, nx_);
+        if (final_step)
+          bad |= huge(du) || huge(dxk) || huge(dpi) || huge(nu_.dtl) || huge(nu_.dtu) ||
+                 huge(nu_.dll) || huge(nu_.dlu);
+        if (keep_step) {  // (otherwise the predictor's du / dx / dpi are not used)
+          stk[kStStep + lane] = du;
+          stk[kStStep + 12 + lane] = dxk;
+          stk[kStStep + 24 + lane] = k > 0 ? dpi : real(0.0);
+        }
+      }
+      dxk = dxn;
+    }
+    // (HPIPM stores step kk in row kk + 1)
+    real* const next =
+        a.stat && lane == 0 ? a.stat + ((size_t)qp * a.stat_rows + iter + 1) * kStatCols : nullptr;
     if (!corr) {
       // alpha_aff, mu_aff, sigma: sum (lam + a dlam)(t + a dt) = S0 + a S1 + a^2 S2
       const real aa = fmin(real(1.0), fmin(gmin(ap), gmin(ad)));
@@ -2437,7 +2023,6 @@ __device__ __forceinline__ void ipm_phase(const IpmArgs<SOFT>& a) {
   }
 }
 
-
 // fp64: 2 workgroups per CU (<= 256 VGPRs); fp32 boxes / C-free rows: 3 (<= 168 VGPRs, 3 waves
 // per SIMD -- the fp32 RB sweep sits just under that cliff and a free allocator crosses it:
 // cone 175 -> 194 ms; with the fp64 stage factorization of C-free rows the sweep needs 178
@@ -2474,8 +2059,8 @@ __device__ __forceinline__ bool solve_done(const ProblemArgsT<real>& a) {
   return a.ctl && __atomic_load_n(a.ctl + kCtlDone, __ATOMIC_RELAXED) != 0;
 }
 
-template <bool FULL, int GEN, int PH, bool SQRT = false, int LQ = 0, bool SOFT = false>
-__global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_kernel(IpmArgs<SOFT> a) {
+template <int GEN, int PH, bool SQRT = false, int LQ = 0, bool SOFT = false>
+__global__ void __launch_bounds__(256, kIpmMinBlocks<GEN>) ipm_phase_kernel(IpmArgs<SOFT> a) {
   if constexpr (PH == kPhInit) {  // this solve's live-QP counters and control words start at 0
     if (a.ctl)
       for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kCtlInts; i += gridDim.x * blockDim.x)
@@ -2483,7 +2068,7 @@ __global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_
   }
   if constexpr (PH != kPhInit && PH != kPhOut)
     if (solve_done(a)) return;
-  ipm_phase<FULL, GEN, PH, SQRT, LQ, SOFT>(a);
+  ipm_phase<GEN, PH, SQRT, LQ, SOFT>(a);
   if constexpr (PH == kPhRB && LQ != 3) report_running(a);  // (3: counted by the 1 launch)
 }
 
@@ -2492,12 +2077,12 @@ __global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase_
 // their records are still in L2 / the Infinity Cache, and the launch count halves.
 // The second phase re-reads the per-QP state the first one wrote (same wave:
 // visible after the workgroup-scope fence).
-template <bool FULL, int GEN, int PH1, int PH2, bool SQRT = false, int LQ = 0, bool SOFT = false>
-__global__ void __launch_bounds__(256, FULL ? kIpmMinBlocks<GEN> : 1) ipm_phase2_kernel(IpmArgs<SOFT> a) {
+template <int GEN, int PH1, int PH2, bool SQRT = false, int LQ = 0, bool SOFT = false>
+__global__ void __launch_bounds__(256, kIpmMinBlocks<GEN>) ipm_phase2_kernel(IpmArgs<SOFT> a) {
   if (solve_done(a)) return;
-  ipm_phase<FULL, GEN, PH1, SQRT, LQ, SOFT>(a);
+  ipm_phase<GEN, PH1, SQRT, LQ, SOFT>(a);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  ipm_phase<FULL, GEN, PH2, SQRT, LQ, SOFT>(a);
+  ipm_phase<GEN, PH2, SQRT, LQ, SOFT>(a);
   if constexpr (PH1 == kPhRB && LQ != 3)  // (lq_fact 1: the LQ launch's QPs are counted, as
     if (!a.lq_redo) report_running(a);   // running, by the Cholesky launch before it)
 }
@@ -2540,7 +2125,7 @@ __global__ void __launch_bounds__(256) compact_running_kernel(const real* __rest
 #endif
 constexpr bool kIpmSplit = SRBD_IPM_SPLIT != 0;
 
-template <bool FULL, int GEN, bool SQRT, int LQ, bool SOFT = false>
+template <int GEN, bool SQRT, int LQ, bool SOFT = false>
 static hipError_t launch_phases(const IpmArgs<SOFT>& a, hipStream_t stream) {
   const int threads = 256;
   const long long lanes = (long long)a.batch * kGroup;
@@ -2567,36 +2152,36 @@ static hipError_t launch_phases(const IpmArgs<SOFT>& a, hipStream_t stream) {
   const bool compact = ctl && a.qp_buf && full_grid.x >= 64;
   // (init covers every QP and clears the control words: no list, whatever they held before)
   b.qp_list = nullptr;
-  hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhInit, false, 0, SOFT>), grid, block, 0, stream, b);
+  hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhInit, false, 0, SOFT>), grid, block, 0, stream, b);
   b.qp_list = compact ? a.qp_buf : nullptr;
   // (SQRT changes RB and how B2, F1, F2 and the outputs apply the record's P)
   for (int it = 0;; ++it) {
     b.launch_it = it;
     if (it >= a.iter_max) {
       if (!a.skip_last_rb) {
-        hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
+        hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhRB, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
         if constexpr (LQ == 1)  // (lq_fact 1: the switched QPs' RB by LQ)
-          hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, 3>), grid, block, 0, stream, b);
+          hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhRB, SQRT, 3>), grid, block, 0, stream, b);
       }
       break;
     }
     if (kIpmSplit) {  // diagnostic schedule: one launch per sweep
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhRB, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhF1, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhRB, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhF1, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
     } else {
-      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhRB, kPhF1, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase2_kernel<GEN, kPhRB, kPhF1, SQRT, LQ, SOFT>), grid, block, 0, stream, b);
     }
     if constexpr (LQ == 1) {
       // HPIPM lq_fact 1: RB -> F1 by LQ of the QPs switched in an earlier iteration, then the
       // predictor step's linear residual of the others (stage-parallel, IR's arithmetic), the
       // switch, and RB -> F1 again by LQ for the QPs it switched (from the same iterate)
-      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhRB, kPhF1, SQRT, 3>), grid, block, 0, stream, b);
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhIRP, SQRT>), dim3(grid.x * (unsigned)(a.N + 1)), block,
+      hipLaunchKernelGGL((ipm_phase2_kernel<GEN, kPhRB, kPhF1, SQRT, 3>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhIRP, SQRT>), dim3(grid.x * (unsigned)(a.N + 1)), block,
                          0, stream, b);
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhLqChk, SQRT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhLqChk, SQRT>), grid, block, 0, stream, b);
       IpmArgs<SOFT> r = b;
       r.lq_redo = 1;
-      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhRB, kPhF1, SQRT, 3>), grid, block, 0, stream, r);
+      hipLaunchKernelGGL((ipm_phase2_kernel<GEN, kPhRB, kPhF1, SQRT, 3>), grid, block, 0, stream, r);
     }
     if (compact) {  // RB(it) has counted its live workgroups: compact for the rest of the solve?
       hipLaunchKernelGGL(compact_decide_kernel, dim3(1), dim3(64), 0, stream, a.ctl, it, a.qp_buf, a.batch);
@@ -2604,10 +2189,10 @@ static hipError_t launch_phases(const IpmArgs<SOFT>& a, hipStream_t stream) {
                          a.ws, a.ws_qp, a.batch, a.qp_buf, a.ctl);
     }
     if (a.pred_corr && kIpmSplit) {
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhB2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
-      hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhF2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhB2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhF2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
     } else if (a.pred_corr) {
-      hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhB2, kPhF2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
+      hipLaunchKernelGGL((ipm_phase2_kernel<GEN, kPhB2, kPhF2, SQRT, 0, SOFT>), grid, block, 0, stream, b);
     }
     // HPIPM's iterative refinement of the corrector step (Balance / Robust): at
     // most itref_corr_max corrections, each after a check of the step's linear residual; a
@@ -2615,13 +2200,13 @@ static hipError_t launch_phases(const IpmArgs<SOFT>& a, hipStream_t stream) {
     if constexpr (!SOFT)  // (the refinement does not carry the slack rows)
     if (a.pred_corr)
       for (int r = 0; r < a.itref_corr_max; ++r) {
-        hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhIR, SQRT>), dim3(grid.x * (unsigned)(a.N + 1)),
+        hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhIR, SQRT>), dim3(grid.x * (unsigned)(a.N + 1)),
                            block, 0, stream, b);
-        hipLaunchKernelGGL((ipm_phase2_kernel<FULL, GEN, kPhIS, kPhF3, SQRT>), grid, block, 0, stream, b);
+        hipLaunchKernelGGL((ipm_phase2_kernel<GEN, kPhIS, kPhF3, SQRT>), grid, block, 0, stream, b);
       }
   }
   b.qp_list = nullptr;  // outputs for every QP
-  hipLaunchKernelGGL((ipm_phase_kernel<FULL, GEN, kPhOut, SQRT, 0, SOFT>), full_grid, block, 0, stream, b);
+  hipLaunchKernelGGL((ipm_phase_kernel<GEN, kPhOut, SQRT, 0, SOFT>), full_grid, block, 0, stream, b);
   return hipGetLastError();
 }
 
@@ -2634,17 +2219,17 @@ hipError_t launch_soft(const ProblemArgsT<real>& a, const SoftArgsT<real>& s, hi
   SoftProblemArgs b;
   static_cast<ProblemArgsT<real>&>(b) = a;
   b.soft = s;
-  if (a.ric_alg) return launch_phases<true, 0, true, 0, true>(b, stream);
-  return launch_phases<true, 0, false, 0, true>(b, stream);
+  if (a.ric_alg) return launch_phases<0, true, 0, true>(b, stream);
+  return launch_phases<0, false, 0, true>(b, stream);
 }
 #else
 // HPIPM's lq_fact (the C-ABI derives it from the mode, with ric_alg != 0 only)
-template <bool FULL, int GEN>
+template <int GEN>
 static hipError_t launch_alg(const ProblemArgsT<real>& a, hipStream_t stream) {
-  if (!a.ric_alg) return launch_phases<FULL, GEN, false, 0>(a, stream);
-  if (a.lq_fact == 2) return launch_phases<FULL, GEN, true, 2>(a, stream);
-  if (a.lq_fact == 1) return launch_phases<FULL, GEN, true, 1>(a, stream);
-  return launch_phases<FULL, GEN, true, 0>(a, stream);
+  if (!a.ric_alg) return launch_phases<GEN, false, 0>(a, stream);
+  if (a.lq_fact == 2) return launch_phases<GEN, true, 2>(a, stream);
+  if (a.lq_fact == 1) return launch_phases<GEN, true, 1>(a, stream);
+  return launch_phases<GEN, true, 0>(a, stream);
 }
 
 hipError_t launch(const ProblemArgsT<real>& a, hipStream_t stream) {
@@ -2653,9 +2238,9 @@ hipError_t launch(const ProblemArgsT<real>& a, hipStream_t stream) {
   if (a.nx != 12 || a.nu != 12) return hipErrorInvalidValue;
   // general rows: GEN 2 with C, GEN 1 when C is absent (NULL = 0, e.g. the friction
   // cone, SRBD_model.cpp:237-260, which constrains u only)
-  if (a.ng > 0 && a.C) return launch_alg<true, 2>(a, stream);
-  if (a.ng > 0) return launch_alg<true, 1>(a, stream);
-  return launch_alg<true, 0>(a, stream);
+  if (a.ng > 0 && a.C) return launch_alg<2>(a, stream);
+  if (a.ng > 0) return launch_alg<1>(a, stream);
+  return launch_alg<0>(a, stream);
 }
 #endif
 

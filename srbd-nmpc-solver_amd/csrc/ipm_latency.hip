@@ -29,6 +29,7 @@
 // barrier-augmented stage blocks (R~, S~, Q~, r~, q~, b~) and the factorization record
 // (K | k rows, P, p, L) in the QP's workspace, where the next recursion reads them from L2
 // one stage ahead of their use.  QP data is read where it lies (HBM / L2).
+#include "ipm_barrier.h"
 #include "kernels.h"
 #include "mfma_lat.h"
 
@@ -46,8 +47,13 @@ namespace ipm_lat {
 
 constexpr int kThreads = 512;
 constexpr int kGroups = kThreads / kGroup;  // one stage per 16-lane group
-constexpr double kThr0 = 0.1;               // HPIPM init_var minimum slack
-constexpr double kTau = 0.995;              // fraction to the boundary
+// the barrier algebra of one inequality pair (ipm_barrier.h), shared with the batched IPM
+using Side = barrier::Side<double>;
+using Bar = barrier::Bar<double>;
+using BarStep = barrier::BarStep<double>;
+using barrier::gsum, barrier::gmax, barrier::gmin, barrier::huge, barrier::step, barrier::nabs;
+using barrier::init_box, barrier::gamma_of, barrier::bar_step, barrier::ratio, barrier::aff_sums;
+constexpr double kThr0 = barrier::kThr0<double>, kStepTau = barrier::kStepTau<double>;
 
 // stage record in the QP's workspace (doubles); K | k rows and P, p as kernels.h kWs*
 constexpr int kRK = 0, kRP = 156, kRp = 234, kRL = 246, kRrs = 324;
@@ -159,9 +165,6 @@ struct Qp {
   }
 };
 
-struct Side {
-  double lb, ub, ml, mu;
-};
 __device__ __forceinline__ Side side_at(const double* lb, const double* ub, const double* lm,
                                         const double* um, size_t o) {
   const double ml = lm ? lm[o] : 1.0, mu = um ? um[o] : 1.0;
@@ -183,12 +186,6 @@ __device__ __forceinline__ Side side_g(const Qp& Q, int k, int r) {
   return side_at(a.lg, a.ug, a.lg_mask, a.ug_mask, ((size_t)Q.q * (Q.N + 1) + k) * a.ng + r);
 }
 
-struct Bar {
-  double ll, lu, tl, tu;
-};
-struct BarStep {
-  double dtl, dtu, dll, dlu;
-};
 __device__ __forceinline__ Bar ld_bar(const double* p, int i) { return Bar{p[i], p[12 + i], p[24 + i], p[36 + i]}; }
 __device__ __forceinline__ void st_bar(double* p, int i, const Bar& b) {
   p[i] = b.ll;
@@ -206,93 +203,6 @@ __device__ __forceinline__ void st_step(double* p, int i, const BarStep& d) {
   p[36 + i] = d.dlu;
 }
 
-// HPIPM init_var for one box-bounded variable: project into the box by thr0, t, lam = mu0 / t
-__device__ __forceinline__ Bar init_box(const Side& s, double& v, double mu0) {
-  Bar bb{0.0, 0.0, 1.0, 1.0};
-  if (s.ml == 0.0 && s.mu == 0.0) return bb;
-  double tl = v - s.lb, tu = s.ub - v;
-  if (s.ml != 0.0 && s.mu != 0.0) {
-    if (tl < kThr0) {
-      if (tu < kThr0) {
-        v = 0.5 * (s.lb + s.ub);
-        tl = tu = kThr0;
-      } else {
-        tl = kThr0;
-        v = s.lb + kThr0;
-        tu = s.ub - v;
-      }
-    } else if (tu < kThr0) {
-      tu = kThr0;
-      v = s.ub - kThr0;
-      tl = v - s.lb;
-    }
-  } else if (s.ml != 0.0) {
-    if (tl < kThr0) {
-      tl = kThr0;
-      v = s.lb + kThr0;
-    }
-  } else if (tu < kThr0) {
-    tu = kThr0;
-    v = s.ub - kThr0;
-  }
-  bb.tl = s.ml != 0.0 ? tl : 1.0;
-  bb.tu = s.mu != 0.0 ? tu : 1.0;
-  bb.ll = s.ml != 0.0 ? mu0 / tl : 0.0;
-  bb.lu = s.mu != 0.0 ? mu0 / tu : 0.0;
-  return bb;
-}
-// Gamma / gamma of one side pair (ipm_box_impl.h gamma_of): rm = lam t + ext - smu
-__device__ __forceinline__ void gamma_of(const Side& s, const Bar& b, double v, double el, double eu,
-                                         double smu, double& G, double& g) {
-  G = 0.0;
-  g = 0.0;
-  if (s.ml != 0.0) {
-    const double rd = v - s.lb - b.tl, rm = b.ll * b.tl + el - smu;
-    G += b.ll / b.tl;
-    g += (rm + b.ll * rd) / b.tl;
-  }
-  if (s.mu != 0.0) {
-    const double rd = s.ub - v - b.tu, rm = b.lu * b.tu + eu - smu;
-    G += b.lu / b.tu;
-    g -= (rm + b.lu * rd) / b.tu;
-  }
-}
-__device__ __forceinline__ BarStep bar_step(const Side& s, const Bar& b, double v, double dv, double el,
-                                            double eu, double smu) {
-  BarStep d{0.0, 0.0, 0.0, 0.0};
-  if (s.ml != 0.0) {
-    d.dtl = (v - s.lb - b.tl) + dv;
-    d.dll = -(b.ll * b.tl + el - smu + b.ll * d.dtl) / b.tl;
-  }
-  if (s.mu != 0.0) {
-    d.dtu = (s.ub - v - b.tu) - dv;
-    d.dlu = -(b.lu * b.tu + eu - smu + b.lu * d.dtu) / b.tu;
-  }
-  return d;
-}
-__device__ __forceinline__ void ratio(const Side& s, const Bar& b, const BarStep& d, double& ap, double& ad) {
-  if (s.ml != 0.0) {
-    if (d.dtl < 0.0) ap = fmin(ap, -b.tl / d.dtl);
-    if (d.dll < 0.0) ad = fmin(ad, -b.ll / d.dll);
-  }
-  if (s.mu != 0.0) {
-    if (d.dtu < 0.0) ap = fmin(ap, -b.tu / d.dtu);
-    if (d.dlu < 0.0) ad = fmin(ad, -b.lu / d.dlu);
-  }
-}
-__device__ __forceinline__ void aff_sums(const Side& s, const Bar& b, const BarStep& d, double& s1, double& s2) {
-  if (s.ml != 0.0) {
-    s1 += b.ll * d.dtl + b.tl * d.dll;
-    s2 += d.dll * d.dtl;
-  }
-  if (s.mu != 0.0) {
-    s1 += b.lu * d.dtu + b.tu * d.dlu;
-    s2 += d.dlu * d.dtu;
-  }
-}
-__device__ __forceinline__ double nabs(double v) { return v == v ? fabs(v) : __builtin_inf(); }
-__device__ __forceinline__ bool huge(double v) { return !(fabs(v) < 1.3e150); }
-__device__ __forceinline__ double stepv(double v, double a, double d) { return a != 0.0 ? fma(a, d, v) : v; }
 // A value every lane holds the same copy of (the block reductions), moved to SGPRs: the kernel
 // loop keeps ~10 such scalars live across the factorization, which needs every VGPR.
 __device__ __forceinline__ double uni(double v) {
@@ -300,28 +210,6 @@ __device__ __forceinline__ double uni(double v) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
   const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ double g16sum(double v) {
-  v += __shfl_xor(v, 8, kGroup);
-  v += __shfl_xor(v, 4, kGroup);
-  v += __shfl_xor(v, 2, kGroup);
-  v += __shfl_xor(v, 1, kGroup);
-  return v;
-}
-__device__ __forceinline__ double g16max(double v) {
-  v = fmax(v, __shfl_xor(v, 8, kGroup));
-  v = fmax(v, __shfl_xor(v, 4, kGroup));
-  v = fmax(v, __shfl_xor(v, 2, kGroup));
-  v = fmax(v, __shfl_xor(v, 1, kGroup));
-  return v;
-}
-__device__ __forceinline__ double g16min(double v) {
-  v = fmin(v, __shfl_xor(v, 8, kGroup));
-  v = fmin(v, __shfl_xor(v, 4, kGroup));
-  v = fmin(v, __shfl_xor(v, 2, kGroup));
-  v = fmin(v, __shfl_xor(v, 1, kGroup));
-  return v;
 }
 
 // 12 strided values p[i * ld] (a row of a column-major block), 0 where p is null
@@ -449,7 +337,7 @@ __device__ __forceinline__ void init_point(const Qp Q, const Lds L) {
       }
     }
   }
-  red_put(L, 0, g16sum(ncl));
+  red_put(L, 0, gsum(ncl));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -525,10 +413,10 @@ __device__ __forceinline__ void stage_pass(const Qp Q, const Lds L, double ap, d
   auto upd = [&](double* bp, const double* sp) {
     Bar b = ld_bar(bp, j);
     const BarStep d = ld_step(sp, j);
-    b.tl = stepv(b.tl, ap, d.dtl);
-    b.tu = stepv(b.tu, ap, d.dtu);
-    b.ll = stepv(b.ll, ad, d.dll);
-    b.lu = stepv(b.lu, ad, d.dlu);
+    b.tl = step(b.tl, ap, d.dtl);
+    b.tu = step(b.tu, ap, d.dtu);
+    b.ll = step(b.ll, ad, d.dll);
+    b.lu = step(b.lu, ad, d.dlu);
     st_bar(bp, j, b);
     return b;
   };
@@ -538,16 +426,16 @@ __device__ __forceinline__ void stage_pass(const Qp Q, const Lds L, double ap, d
     Bar bu{0, 0, 1, 1}, bx{0, 0, 1, 1};
     if (el) {
       if (k < N) {
-        uj = stepv(L.u()[k * 12 + j], ap, L.du()[k * 12 + j]);
+        uj = step(L.u()[k * 12 + j], ap, L.du()[k * 12 + j]);
         L.u()[k * 12 + j] = uj;
-        xnj = stepv(xo[(k + 1) * 12 + j], ap, L.dx()[(k + 1) * 12 + j]);
-        pinj = stepv(po[(k + 1) * 12 + j], ad, L.dpi()[(k + 1) * 12 + j]);
+        xnj = step(xo[(k + 1) * 12 + j], ap, L.dx()[(k + 1) * 12 + j]);
+        pinj = step(po[(k + 1) * 12 + j], ad, L.dpi()[(k + 1) * 12 + j]);
       }
       xj = xo[k * 12 + j];
       pij = po[k * 12 + j];
       if (k > 0) {  // (x_0 = x0 is fixed; pi_0 is not an iterate)
-        xj = stepv(xj, ap, L.dx()[k * 12 + j]);
-        pij = stepv(pij, ad, L.dpi()[k * 12 + j]);
+        xj = step(xj, ap, L.dx()[k * 12 + j]);
+        pij = step(pij, ad, L.dpi()[k * 12 + j]);
       }
       xw[k * 12 + j] = xj;
       pw[k * 12 + j] = pij;
@@ -710,12 +598,12 @@ __device__ __forceinline__ void stage_pass(const Qp Q, const Lds L, double ap, d
       rk[kRq + j] = gx + gam_x + gpx;
     }
   }
-  red_put(L, 0, g16max(mg));
-  red_put(L, 1, g16max(mb));
-  red_put(L, 2, g16max(md));
-  red_put(L, 3, g16max(mm));
-  red_put(L, 4, g16sum(el ? musum : 0.0));
-  red_put(L, 5, g16sum(objl));
+  red_put(L, 0, gmax(mg));
+  red_put(L, 1, gmax(mb));
+  red_put(L, 2, gmax(md));
+  red_put(L, 3, gmax(mm));
+  red_put(L, 4, gsum(el ? musum : 0.0));
+  red_put(L, 5, gsum(objl));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1193,11 +1081,11 @@ __device__ __forceinline__ void step_pass(const Qp Q, const Lds L, double smu, b
       }
     }
   }
-  red_put(L, 0, g16min(ap));
-  red_put(L, 1, g16min(ad));
-  red_put(L, 2, g16sum(s1));
-  red_put(L, 3, g16sum(s2));
-  red_put(L, 4, g16max(bad ? 1.0 : 0.0));
+  red_put(L, 0, gmin(ap));
+  red_put(L, 1, gmin(ad));
+  red_put(L, 2, gsum(s1));
+  red_put(L, 3, gsum(s2));
+  red_put(L, 4, gmax(bad ? 1.0 : 0.0));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1393,8 +1281,8 @@ __device__ __forceinline__ void lin_res_pass(const Qp Q, const Lds L) {
       L.v12(L.ref_b())[k * 12 + j] = rb;
     }
   }
-  red_put(L, 0, g16max(ng));
-  red_put(L, 1, g16max(nb));
+  red_put(L, 0, gmax(ng));
+  red_put(L, 1, gmax(nb));
 }
 
 // The correction (solved by the corrector's recursion on the check's residual: ddx in gtu, k, p
@@ -1492,9 +1380,9 @@ __device__ __forceinline__ void corr_apply_pass(const Qp Q, const Lds L) {
       }
     }
   }
-  red_put(L, 0, g16min(ap));
-  red_put(L, 1, g16min(ad));
-  red_put(L, 4, g16max(bad ? 1.0 : 0.0));
+  red_put(L, 0, gmin(ap));
+  red_put(L, 1, gmin(ad));
+  red_put(L, 4, gmax(bad ? 1.0 : 0.0));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1746,8 +1634,8 @@ __global__ void __launch_bounds__(kThreads, 1) ipm_latency_kernel(ProblemArgsT<d
       ap = fmin(ap, ad);
       ad = ap;
     }
-    alpha_p = uni(fmin(1.0, kTau * ap));
-    alpha_d = uni(fmin(1.0, kTau * ad));
+    alpha_p = uni(fmin(1.0, kStepTau * ap));
+    alpha_d = uni(fmin(1.0, kStepTau * ad));
     if (next) {
       next[3] = alpha_p;
       next[4] = alpha_d;

@@ -129,6 +129,10 @@ constexpr int kGenChunk = 112;
 // parts (C = NULL kernels): D'gamma_pred [12] (RB), D'e [12] with e = d gamma / d(sigma mu)
 // (RB), D'z [12] with z the predictor-product term of gamma_corr (F1)
 constexpr int kGenVec = 36;
+// workspace elements per stage of a problem with nch 12-row chunks of general rows
+constexpr size_t ipm_stage_stride(int nch) {
+  return (size_t)kIpmStage + (size_t)nch * kGenChunk + (nch ? kGenVec : 0);
+}
 
 size_t ws_doubles_ipm(int N, int ng);  // elements per QP (either precision)
 
