@@ -32,6 +32,8 @@
  *   srbd_qp_srbd_advance_f64     what a controller does between two steps: apply u[0], move the
  *                                plant, shift the previous solution by one stage.
  *   srbd_qp_srbd_rollout_f64     T ticks of the closed receding-horizon loop around the step.
+ *   srbd_qp_srbd_set_robots_f64  per-robot mass, inertia, friction and weights for all of the
+ *                                above: what the controller believes, and the true robot.
  *
  * ------------------------------------------------------------------------
  * Problem (per QP, stages k = 0..N), identical to hpipm::OcpQp
@@ -571,6 +573,45 @@ int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_param
                              const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
                              const srbd_rollout_f64* roll,
                              double* xs, double* us, double* x, double* alpha);
+
+/* ------------------------------------------------------------------------
+ * Robots (additive to ABI 12): per-robot overrides of six constants of srbd_model_params,
+ * for batches whose robots differ (domain randomisation: the plant is not the model the
+ * controller believes) or that sweep a weight or a friction coefficient over one plan.
+ * They attach to the handle in one of two roles, and every SRBD entry point issued
+ * afterwards on that handle (linearise, line search, NMPC step, advance, rollout; plain and
+ * _plan_ alike) reads robot i's values at row i.
+ *   SRBD_QP_ROBOTS_MODEL  what the controller believes; all six fields apply.
+ *     Linearisation: A through L^-1, B through 1 / mass, b through the RK4 of the dynamics;
+ *     the friction barrier's part of R / r with the robot's mu and R; Q, q with the robot's
+ *     Q and Qf (qf_scale stays params->qf_scale); with CONE, the mu entries of D and lg.
+ *     Line search: merit, gradient and shooting defect.  Advance: the model step that
+ *     makes the new last stage xs[N].
+ *   SRBD_QP_ROBOTS_PLANT  the true robot; only mass and Lbody may be given.  Read by the
+ *     plant step of srbd_qp_srbd_advance_f64 (and so by the rollout's) and by nothing else;
+ *     the wrench's force / mass uses the plant's mass.  A field that is NULL here, or the
+ *     whole role when it is not set, is the MODEL role's value, then params'.
+ * The call copies the six pointers and does no device work.  The arrays are device memory
+ * with at least `batch` rows of each later call; they are read by the launched kernels: keep
+ * them alive and unchanged until those have finished.  robots == NULL, or a struct whose
+ * fields are all NULL, clears the role; with both roles clear the calls are what they are
+ * without this entry point: the same kernels, the same bits.
+ * Caller's contract (device data, not checked): mass, Lbody, mu, R > 0 and Q, Qf >= 0.
+ * Checks: NULL handle, a role other than the two, or a PLANT role with mu, Q, Qf or R are
+ * SRBD_QP_EINVAL; a handle without nx = nu = 12 is SRBD_QP_EDIM.
+ * Not per robot (out of scope): u_lo / u_hi, fmin, Lfx / Lfz, dt, the barrier constants;
+ * srbd_qp_multi_* (a multi-device handle has no roles) and the hpipm-cpp shim.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_robots_f64 { /* device memory, fp64, dense; NULL field = the value in srbd_model_params */
+  const double* mass;    /* [batch]      */
+  const double* Lbody;   /* [batch][3]   body inertia diagonal */
+  const double* mu;      /* [batch]      friction coefficient  */
+  const double* Q;       /* [batch][12]  */
+  const double* Qf;      /* [batch][12]  (qf_scale stays the one in srbd_model_params) */
+  const double* R;       /* [batch]      */
+} srbd_robots_f64;
+enum { SRBD_QP_ROBOTS_MODEL = 0, SRBD_QP_ROBOTS_PLANT = 1 };
+int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f64* robots);
 
 /* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,

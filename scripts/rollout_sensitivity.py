@@ -12,6 +12,13 @@ For each case (constraints, alpha_reset) of the test and a seed of rollout_host.
 
     python scripts/rollout_sensitivity.py --seed 30            # the table of the test's seed
     python scripts/rollout_sensitivity.py --search 20 40       # seeds that meet the conditions
+
+With --robots the same for tests/test_gpu_robots.py's rollout: per-robot model
+parameters from robots_host.draw at seed + 100, the true robots from robots_host.draw_plant at
+seed + 200, two plant substeps, through robots_host.closed_loop; and how far the mismatch moves
+x_log (the same loop with plant = model).
+
+    python scripts/rollout_sensitivity.py --robots --seed 30
 """
 import argparse
 import sys
@@ -24,6 +31,7 @@ sys.path.insert(0, str(REPO / "tests"))
 sys.path.insert(0, str(REPO / "oracle"))
 
 import helpers  # noqa: E402
+import robots_host as BH  # noqa: E402
 import rollout_host as RH  # noqa: E402
 
 NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
@@ -33,8 +41,14 @@ CASES = [(c, a) for c in ("none", "box_u") for a in (0.0, 1.0)]
 B, N, T = 4, 10, 4
 
 
+ROBOTS = None  # --robots: (model list, plant list)
+
+
 def run(sm, oracle, p, case, inputs):
     xs, us, x, alpha, plan = inputs
+    if ROBOTS:
+        return BH.closed_loop(sm, oracle, ROBOTS[0], ROBOTS[1], plan, xs, us, x, alpha, T, NMPC, 15, case[0],
+                              substeps=2, alpha_reset=case[1])
     return RH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, 15, case[0], alpha_reset=case[1])
 
 
@@ -48,19 +62,29 @@ def conditions(sm, oracle, p, seed):
 
 
 def main():
+    global ROBOTS
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=30)
     ap.add_argument("--search", type=int, nargs=2, metavar=("FROM", "TO"))
     ap.add_argument("--draws", type=int, default=3)
+    ap.add_argument("--robots", action="store_true")
     a = ap.parse_args()
     sm, oracle = helpers.load_package().srbd_model, helpers.load_oracle()
     p = sm.SrbdParams()
+
+    def set_robots(seed):
+        global ROBOTS
+        if a.robots:
+            model = BH.draw(p, B, seed + 100)
+            ROBOTS = (model, BH.draw_plant(model, seed + 200))
     if a.search:
         for seed in range(a.search[0], a.search[1]):
+            set_robots(seed)
             _, c = conditions(sm, oracle, p, seed)
             ok = all(m >= 1e-6 and len(its) >= 2 for m, its, _ in c.values())
             print(seed, "OK " if ok else "-- ", {k: (f"{m:.1e}", its) for k, (m, its, _) in c.items()}, flush=True)
         return
+    set_robots(a.seed)
     inputs, c = conditions(sm, oracle, p, a.seed)
     xs, us, x, alpha, plan = inputs
     for case in CASES:
@@ -77,6 +101,12 @@ def main():
             print(f"  draw {d}: same iteration counts {same}")
         fmt = lambda v: "(" + ", ".join(f"{e:.1e}" for e in v) + ")"
         print(f"    {case!r}: ({fmt(dx)}, {fmt(du)}),")
+        if ROBOTS:
+            both = ROBOTS
+            ROBOTS = (both[0], both[0])
+            same_plant = run(sm, oracle, p, case, inputs)
+            ROBOTS = both
+            print(f"    plant != model moves x_log by {np.abs(base['x_log'] - same_plant['x_log']).max():.2e}")
 
 
 if __name__ == "__main__":

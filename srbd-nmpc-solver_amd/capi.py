@@ -155,6 +155,61 @@ def _plan_ref(plan: Optional["Plan"], B: int, N: int, device):
     return None if plan is None else C.byref(plan.struct(B, N, device))
 
 
+class RobotsStruct(C.Structure):
+    """srbd_robots_f64: device pointers, NULL = the value in srbd_model_params."""
+    _fields_ = [(n, _dp) for n in ("mass", "Lbody", "mu", "Q", "Qf", "R")]
+
+
+ROBOT_ROLES = {"model": 0, "plant": 1}
+
+
+class Robots:
+    """Per-robot overrides of six constants of ModelParams (srbd_robots_f64) for
+    Handle.set_robots: torch fp64 device tensors, each optional.
+
+    mass [B]   Lbody [B][3]   mu [B]   Q [B][12]   Qf [B][12]   R [B]
+
+    B is the same in every field and at least the batch of the calls that follow.  As the
+    handle's "model" role all six apply; its "plant" role (the true robot that srbd_advance and
+    srbd_rollout integrate) takes mass and Lbody only.  Dtype, contiguity, shapes and device
+    are checked here, with ValueError, before the library sees the pointers."""
+    FIELDS = {"mass": (), "Lbody": (3,), "mu": (), "Q": (12,), "Qf": (12,), "R": ()}
+    PLANT_FIELDS = ("mass", "Lbody")
+
+    def __init__(self, mass=None, Lbody=None, mu=None, Q=None, Qf=None, R=None):
+        self.mass, self.Lbody, self.mu, self.Q, self.Qf, self.R = mass, Lbody, mu, Q, Qf, R
+
+    def struct(self, role: str = "model", device=None) -> RobotsStruct:
+        """The C struct for `role`; ValueError on a field the role does not take or a tensor
+        that does not fit.  `device`: the handle's torch device."""
+        import torch
+        if role not in ROBOT_ROLES:
+            raise ValueError(f"unknown robots role {role!r}, expected 'model' or 'plant'")
+        rs = RobotsStruct()
+        rows = None
+        for name, tail in self.FIELDS.items():
+            t = getattr(self, name)
+            if t is None:
+                continue
+            if role == "plant" and name not in self.PLANT_FIELDS:
+                raise ValueError(f"robots.{name}: the plant role takes mass and Lbody only")
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"robots.{name} must be a torch.float64 tensor")
+            if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < 1:
+                raise ValueError(f"robots.{name} has shape {tuple(t.shape)}, expected {('B',) + tail}")
+            if rows is not None and t.shape[0] != rows:
+                raise ValueError(f"robots.{name} has {t.shape[0]} rows, the other fields {rows}")
+            rows = t.shape[0]
+            if not t.is_contiguous():
+                raise ValueError(f"robots.{name} must be contiguous")
+            if t.device.type != "cuda" or (device is not None and t.device != device):
+                raise ValueError(f"robots.{name} is on {t.device}, the handle on "
+                                 f"{device if device is not None else 'a GPU'}")
+            setattr(rs, name, t.data_ptr())
+        self.rows = rows
+        return rs
+
+
 class AdvanceStruct(C.Structure):
     """srbd_advance_f64."""
     _fields_ = [("substeps", C.c_int), ("wrench", _dp)]
@@ -293,6 +348,9 @@ def lib():
                                                    C.POINTER(Settings), C.c_int, C.c_int,
                                                    C.POINTER(RolloutStruct)] + [C.c_void_p] * 4
             L.srbd_qp_srbd_rollout_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_srbd_set_robots_f64"):  # robots (older builds: A/B runs)
+            L.srbd_qp_srbd_set_robots_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(RobotsStruct)]
+            L.srbd_qp_srbd_set_robots_f64.restype = C.c_int
         L.srbd_qp_abi_version.argtypes = []
         L.srbd_qp_abi_version.restype = C.c_int
         _lib = L
@@ -413,6 +471,24 @@ class Handle:
             return
         f = lib().srbd_qp_solve_host_f32 if isinstance(data, Data32) else lib().srbd_qp_solve_host_f64
         check(f(self._h, int(batch), C.byref(settings), C.byref(data), C.byref(sol)), f.__name__)
+
+    def set_robots(self, model: Optional["Robots"] = None, plant: Optional["Robots"] = None) -> None:
+        """srbd_qp_srbd_set_robots_f64 for both roles: every srbd_* call on this handle afterwards
+        reads robot i's constants at row i of `model` (what the controller believes: mass, Lbody,
+        mu, Q, Qf, R) and, in the plant step of srbd_advance / srbd_rollout, of `plant` (the true
+        robot: mass, Lbody; a missing field is the model's).  None clears a role.  The handle
+        keeps the Robots, and so their tensors, alive until they are replaced; do not modify the
+        tensors while launches that read them are in flight."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        # both validated before either is set
+        structs = [(role, r, None if r is None else r.struct(role, dev))
+                   for role, r in (("model", model), ("plant", plant))]
+        for role, r, rs in structs:
+            check(lib().srbd_qp_srbd_set_robots_f64(self._h, ROBOT_ROLES[role],
+                                                    None if rs is None else C.byref(rs)),
+                  "srbd_qp_srbd_set_robots_f64")
+        self._robots = (model, plant)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -587,6 +663,13 @@ def model_params(p) -> ModelParams:
     return m
 
 
+def _check_robots(handle, B) -> None:
+    """The handle's robots (Handle.set_robots) are read at rows 0..B-1: ValueError if one has fewer."""
+    for r in getattr(handle, "_robots", ()):
+        if r is not None and r.rows is not None and r.rows < int(B):
+            raise ValueError(f"the handle's robots have {r.rows} rows, the batch {int(B)}")
+
+
 def _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream):
     """srbd_qp_srbd_linearize_f64, or the _plan_ entry point when a plan is given."""
     tail = (SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()), C.c_void_p(us.data_ptr()),
@@ -614,6 +697,7 @@ def srbd_linearize(handle: Handle, xs, us, constraints: str = "none",
     N = N1 - 1
     dev = xs.device
     plan_ref = _plan_ref(plan, B, N, dev)
+    _check_robots(handle, B)
     f = dict(dtype=torch.float64, device=dev)
     if out is not None:  # caller-owned buffers from a previous call (no allocation)
         t = out
@@ -657,6 +741,7 @@ def srbd_linesearch(handle: Handle, xs, us, dx, du, alpha, params: Optional[Mode
     import torch
     B = xs.shape[0]
     plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
+    _check_robots(handle, B)
     merit = torch.empty(B, 3, dtype=torch.float64, device=xs.device)
     conv = torch.empty(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
@@ -688,6 +773,7 @@ def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
     import torch
     B = xs.shape[0]
     plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
+    _check_robots(handle, B)
     it = torch.zeros(B, dtype=torch.int32, device=xs.device)
     conv = torch.zeros(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
@@ -736,6 +822,7 @@ def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wr
     if wrench is not None:
         _check_f64("wrench", wrench, (B, 6), dev)
     plan_ref = _plan_ref(plan, B, N, dev)
+    _check_robots(handle, B)
     u0 = torch.empty(B, 12, dtype=torch.float64, device=dev)
     adv = AdvanceStruct(int(substeps), _tensor_ptr(wrench) or None)
     p = params or default_model_params()
@@ -773,6 +860,7 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
         _check_f64("wrench", wrench, (B, max(T, 0), 6), dev)
     P = N + T - 1 if plan_stages is None else int(plan_stages)
     plan_ref = _plan_ref(plan, B, P, dev)
+    _check_robots(handle, B)
     rows = max(T, 0)
     x_log = torch.zeros(B, rows + 1, 12, dtype=torch.float64, device=dev)
     u_log = torch.zeros(B, rows, 12, dtype=torch.float64, device=dev)

@@ -237,7 +237,8 @@ hipError_t launch_srbd_linesearch(const srbd_model_params& p, const srbd_linesea
                                   int batch, int N, double* xs, double* us, const double* dx,
                                   const double* du, double* alpha, double* merit, int* converged,
                                   hipStream_t stream, const int* done = nullptr,
-                                  const srbd_plan_f64* plan = nullptr);
+                                  const srbd_plan_f64* plan = nullptr,
+                                  const srbd_robots_f64* robots = nullptr);
 hipError_t launch_nmpc_prep(int batch, int N, int it, const double* xs, const double* x0,
                             double* dx0, int* done, int* sqp_iter, int* converged,
                             hipStream_t stream);
@@ -246,7 +247,8 @@ hipError_t launch_nmpc_after(int batch, int it, const int* conv, int* done, int*
 hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, int mode,
                                  const double* xs, const double* us,
                                  const srbd_qp_data_f64& out, hipStream_t stream,
-                                 const srbd_plan_f64* plan = nullptr);
+                                 const srbd_plan_f64* plan = nullptr,
+                                 const srbd_robots_f64* robots = nullptr);
 
 // srbd_rollout.hip: one tick's plant step and shift of the guess (srbd_qp_srbd_advance_f64).
 // The per-robot outputs carry a stride (doubles / ints per robot), so that the rollout writes
@@ -265,8 +267,12 @@ struct AdvanceIo {
   int *it_log, *cv_log;
   long long log_stride;
 };
+// `robots`: the handle's MODEL role (lane 1, and lane 0 where the PLANT role has no value);
+// `plant`: its PLANT role (lane 0: mass and Lbody).  Either may be NULL.
 hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, const AdvanceIo& io,
-                               const srbd_plan_f64* plan, hipStream_t stream);
+                               const srbd_plan_f64* plan, hipStream_t stream,
+                               const srbd_robots_f64* robots = nullptr,
+                               const srbd_robots_f64* plant = nullptr);
 // Up to four strided row copies, dst[r * dstride + e] = src[r * sstride + e] (e < width,
 // r < batch), and alpha[r] = alpha_value when alpha is given, in one launch.
 struct RolloutRow {

@@ -36,9 +36,9 @@ struct LinArgs {
   srbd_qp_data_f64 out;  // device pointers to fill (const dropped below)
   double qf_scale;
 };
-// with a plan, its four pointers follow the block
-template <bool PLAN>
-struct LinArgsT : LinArgs, PlanArgs<PLAN> {};
+// with a plan, its four pointers follow the block; with robots, their six
+template <bool PLAN, bool ROBOT>
+struct LinArgsT : LinArgs, PlanArgs<PLAN>, RobotArgs<ROBOT> {};
 
 // Per-stage descriptor of the matrices a (QP, stage) thread hands to its wave: the
 // nonzero 3x3 Jacobian blocks and the friction-barrier R (diagonal + 4 off-diagonal pairs
@@ -47,6 +47,9 @@ struct LinArgsT : LinArgs, PlanArgs<PLAN> {};
 // range of the [batch][N][144] arrays): every store instruction fills whole lines.
 constexpr int kDJ00 = 0, kDJ01 = 9, kDFs = 18, kDP0 = 21, kDP1 = 24, kDRd = 27, kDRo = 39,
               kDesc = 48;  // (slot 47: the constant 1.0)
+// With robots, two more slots carry what the wave's stores read per stage and not from
+// Model::p: 1 / mass (B) and mu (D).
+constexpr int kDIm = 48, kDMu = 49, kDescRobot = 50;
 constexpr int kLinThreads = 64;
 
 // The element functions below are branch-free (index and coefficient by selects, one LDS
@@ -114,9 +117,12 @@ __device__ __forceinline__ double r_at(const double* d, int i, int j) {
 // S (= 0) are written by srbd_lin_cost_kernel / a memset.
 // With a plan, the thread reads its stage's feet and force limits at t * 3 and t * 2: adjacent
 // threads, adjacent memory.
-template <bool PLAN>
-__global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, LinArgsT<PLAN> a) {
-  __shared__ double desc[kLinThreads * kDesc];
+// With robots, the thread loads its robot's scalars at qp: a wave holds stages of several
+// robots, so they are per-lane values; the N threads of one robot read the same addresses.
+template <bool PLAN, bool ROBOT>
+__global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, LinArgsT<PLAN, ROBOT> a) {
+  constexpr int kD = ROBOT ? kDescRobot : kDesc;
+  __shared__ double desc[kLinThreads * kD];
   const int N = a.N;
   const long long nst_all = (long long)a.batch * N;
   const long long t0 = (long long)blockIdx.x * kLinThreads;
@@ -125,24 +131,25 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
   const double dt = p.dt;
   if (t < nst_all) {
     const int qp = (int)(t / N), k = (int)(t % N);
-    double* dsc = desc + threadIdx.x * kDesc;
+    double* dsc = desc + threadIdx.x * kD;
     const double* x = a.xs + ((size_t)qp * (N + 1) + k) * 12;
     const double* u = a.us + (size_t)t * 12;
     const double* xn = x + 12;
     const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)t);
+    const RobotVals<ROBOT> rb = load_robot<ROBOT>(p, a, (size_t)qp);
     // ---- shooting dynamics (GetShootingDynamic, SRBD_model.cpp:178-235): b = RK4(x, u) - x_next ----
     {
       double k1[12], k2[12], k3[12], k4[12], xt[12];
-      m.f(sv, x, u, k1);
+      m.f(sv, rb, x, u, k1);
 #pragma unroll
       for (int i = 0; i < 12; ++i) xt[i] = x[i] + 0.5 * dt * k1[i];
-      m.f(sv, xt, u, k2);
+      m.f(sv, rb, xt, u, k2);
 #pragma unroll
       for (int i = 0; i < 12; ++i) xt[i] = x[i] + 0.5 * dt * k2[i];
-      m.f(sv, xt, u, k3);
+      m.f(sv, rb, xt, u, k3);
 #pragma unroll
       for (int i = 0; i < 12; ++i) xt[i] = x[i] + dt * k3[i];
-      m.f(sv, xt, u, k4);
+      m.f(sv, rb, xt, u, k4);
       double* b = const_cast<double*>(a.out.b) + (size_t)t * 12;
 #pragma unroll
       for (int i = 0; i < 12; ++i)
@@ -151,7 +158,7 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
     // ---- Jacobian blocks (A = I + dt jfx, B = dt jfu) into the descriptor ----
     {
       M3 J00, J01, Sf, S0, S1;
-      m.jac_blocks(sv, x, u, J00, J01, Sf, S0, S1);
+      m.jac_blocks(sv, rb, x, u, J00, J01, Sf, S0, S1);
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -171,15 +178,15 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
     double rv[12], rd[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
-      rv[i] = p.R * u[i];
-      rd[i] = p.R;
+      rv[i] = rb.R(p) * u[i];
+      rd[i] = rb.R(p);
     }
     double fc[24];
 #pragma unroll
     for (int leg = 0; leg < 2; ++leg) {
       const int o = 6 * leg;
       const double fx = u[o], fy = u[o + 1], fz = u[o + 2], tx = u[o + 3], ty = u[o + 4], tz = u[o + 5];
-      const double mu = p.mu, Lx = p.Lfx, Lz = p.Lfz;
+      const double mu = rb.mu(p), Lx = p.Lfx, Lz = p.Lfz;
       double v[12], db[12], ddb[12];
       v[0] = -fx + mu * fz;
       v[1] = -fy + mu * fz;
@@ -220,6 +227,10 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
 #pragma unroll
     for (int i = 0; i < 12; ++i) dsc[kDRd + i] = rd[i];
     dsc[kDOne] = 1.0;
+    if constexpr (ROBOT) {
+      dsc[kDIm] = 1.0 / rb.mass(p);
+      dsc[kDMu] = rb.mu(p);
+    }
     double* rr = const_cast<double*>(a.out.r) + (size_t)t * 12;
 #pragma unroll
     for (int i = 0; i < 12; ++i) rr[i] = rv[i];
@@ -256,17 +267,22 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
   for (int v = threadIdx.x; v < nst * 72; v += kLinThreads) {
     const int st = v / 72, o = 2 * (v - st * 72);
     const int j = o / 12, i = o - j * 12;
-    const double* d = desc + st * kDesc;
+    const double* d = desc + st * kD;
     st_nt(&A2[v], a_at(d, i, j, dt), a_at(d, i + 1, j, dt));
-    st_nt(&B2[v], b_at(d, i, j, dt, im), b_at(d, i + 1, j, dt, im));
+    if constexpr (ROBOT)
+      st_nt(&B2[v], b_at(d, i, j, dt, d[kDIm]), b_at(d, i + 1, j, dt, d[kDIm]));
+    else
+      st_nt(&B2[v], b_at(d, i, j, dt, im), b_at(d, i + 1, j, dt, im));
     st_nt(&R2[v], r_at(d, i, j), r_at(d, i + 1, j));
   }
-  if (a.mode == 2) {  // D = Ac (24 x 12, column-major), the same on every stage
+  if (a.mode == 2) {  // D = Ac (24 x 12, column-major), the same on every stage of a robot
     double2* D2 = reinterpret_cast<double2*>(const_cast<double*>(a.out.D) + t0 * 288);
     for (int v = threadIdx.x; v < nst * 144; v += kLinThreads) {
       const int o = 2 * (v % 144);
       const int j = o / 24, c = o - j * 24;
-      D2[v] = make_double2(m.ac(c, j), m.ac(c + 1, j));
+      double mu = p.mu;
+      if constexpr (ROBOT) mu = desc[(v / 144) * kD + kDMu];
+      D2[v] = make_double2(m.ac(c, j, mu), m.ac(c + 1, j, mu));
     }
   }
 }
@@ -275,8 +291,15 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
 // N; prepareQpStructures, NMPC_solver.cpp:286-313), element-wise and coalesced; with the
 // cone, the terminal stage's rows are absent (masked).
 // With a plan, x_ref is read at the same element index e as xs.
-template <bool PLAN>
-__global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PLAN> a) {
+// With robots, the weight is element i of row blk / (N + 1) of Q or Qf.
+__device__ __forceinline__ double cost_w(const srbd_model_params& p, const srbd_robots_f64& rb, long long blk,
+                                         int N, int k, int i) {
+  const double* wr = k < N ? rb.Q : rb.Qf;
+  if (wr) return wr[(size_t)(blk / (N + 1)) * 12 + i];
+  return k < N ? p.Q[i] : p.Qf[i];
+}
+template <bool PLAN, bool ROBOT>
+__global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PLAN, ROBOT> a) {
   const srbd_model_params& p = m.p;
   const int N = a.N;
   const long long nq2 = (long long)a.batch * (N + 1) * 72;  // double2 of Q
@@ -286,17 +309,31 @@ __global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PL
     const long long blk = g / 72;
     const int o = 2 * (int)(g - blk * 72);
     const int k = (int)(blk % (N + 1)), j = o / 12, i = o - j * 12;
-    const double* w = k < N ? p.Q : p.Qf;
     const double sc = k < N ? 1.0 : a.qf_scale;
-    st_nt(&reinterpret_cast<double2*>(const_cast<double*>(a.out.Q))[g], i == j ? sc * w[i] : 0.0,
-          i + 1 == j ? sc * w[i + 1] : 0.0);
+    if constexpr (ROBOT) {
+      // every lane loads both weights and selects: loading only in the 12 of a block's 72 pairs
+      // that hold a diagonal element was slower (0.47 against 0.44 ms at 65536 x 20)
+      const double w0 = cost_w(p, a, blk, N, k, i), w1 = cost_w(p, a, blk, N, k, i + 1);
+      st_nt(&reinterpret_cast<double2*>(const_cast<double*>(a.out.Q))[g], i == j ? sc * w0 : 0.0,
+            i + 1 == j ? sc * w1 : 0.0);
+    } else {
+      const double* w = k < N ? p.Q : p.Qf;
+      st_nt(&reinterpret_cast<double2*>(const_cast<double*>(a.out.Q))[g], i == j ? sc * w[i] : 0.0,
+            i + 1 == j ? sc * w[i + 1] : 0.0);
+    }
   } else if (g < nq2 + nq) {
     const long long e = g - nq2;
     const long long blk = e / 12;
     const int i = (int)(e - blk * 12), k = (int)(blk % (N + 1));
-    const double* w = k < N ? p.Q : p.Qf;
     const double sc = k < N ? 1.0 : a.qf_scale;
-    const_cast<double*>(a.out.q)[e] = sc * w[i] * (a.xs[e] - x_ref_at<PLAN>(p, a, (size_t)e, i));
+    double wi;
+    if constexpr (ROBOT) {
+      wi = cost_w(p, a, blk, N, k, i);
+    } else {
+      const double* w = k < N ? p.Q : p.Qf;
+      wi = w[i];
+    }
+    const_cast<double*>(a.out.q)[e] = sc * wi * (a.xs[e] - x_ref_at<PLAN>(p, a, (size_t)e, i));
   } else if (a.mode == 2 && g < nq2 + nq + (long long)a.batch * 24) {
     const long long e = g - nq2 - nq;
     const long long qp = e / 24;
@@ -332,23 +369,23 @@ struct LsArgs {
   double qf_scale;
   const int* done;  // optional: robots whose SQP loop has stopped are left untouched
 };
-template <bool PLAN>
-struct LsArgsT : LsArgs, PlanArgs<PLAN> {};
+template <bool PLAN, bool ROBOT>
+struct LsArgsT : LsArgs, PlanArgs<PLAN>, RobotArgs<ROBOT> {};
 
 // the 24 friction-cone / torque-limit rows f(u) of GetConstrain (SRBD_model.cpp:237-260,
 // R_f = I), two nonzeros each: the explicit form of bc(c) + sum_j ac(c, j) u_j
 template <class St>
-__device__ __forceinline__ void cone_rows(const srbd_model_params& p, const St& s, const double* u,
+__device__ __forceinline__ void cone_rows(const srbd_model_params& p, const St& s, double mu, const double* u,
                                           double* v) {
 #pragma unroll
   for (int leg = 0; leg < 2; ++leg) {
     const int o = 6 * leg;
     const double fx = u[o], fy = u[o + 1], fz = u[o + 2], tx = u[o + 3], ty = u[o + 4], tz = u[o + 5];
     double* w = v + 12 * leg;
-    w[0] = -fx + p.mu * fz;
-    w[1] = -fy + p.mu * fz;
-    w[2] = fx + p.mu * fz;
-    w[3] = fy + p.mu * fz;
+    w[0] = -fx + mu * fz;
+    w[1] = -fy + mu * fz;
+    w[2] = fx + mu * fz;
+    w[3] = fy + mu * fz;
     w[4] = -fz + s.fz_max(p, leg);
     w[5] = fz - p.fmin;
     w[6] = p.Lfx * fz - ty;
@@ -360,14 +397,15 @@ __device__ __forceinline__ void cone_rows(const srbd_model_params& p, const St& 
   }
 }
 // ju += Ac' db (the same sparsity)
-__device__ __forceinline__ void cone_grad(const srbd_model_params& p, const double* db, double* ju) {
+__device__ __forceinline__ void cone_grad(const srbd_model_params& p, double mu, const double* db,
+                                          double* ju) {
 #pragma unroll
   for (int leg = 0; leg < 2; ++leg) {
     const int o = 6 * leg;
     const double* d = db + 12 * leg;
     ju[o + 0] += -d[0] + d[2];
     ju[o + 1] += -d[1] + d[3];
-    ju[o + 2] += p.mu * (d[0] + d[1] + d[2] + d[3]) - d[4] + d[5] + p.Lfx * (d[6] + d[7]) +
+    ju[o + 2] += mu * (d[0] + d[1] + d[2] + d[3]) - d[4] + d[5] + p.Lfx * (d[6] + d[7]) +
                  p.Lfz * (d[8] + d[9]);
     ju[o + 3] += -d[10] + d[11];
     ju[o + 4] += -d[6] + d[7];
@@ -380,9 +418,11 @@ __device__ __forceinline__ void cone_grad(const srbd_model_params& p, const doub
 // the model (a loop over the four slopes) and the cone rows from their sparsity: a small
 // register footprint for this latency-bound kernel.
 // With a plan the stage's rows are loaded here, once for the four slopes.
-template <bool PLAN>
-__device__ void stage_merit(const Model& m, const LsArgsT<PLAN>& a, int qp, int k, double al, bool grad,
-                            double& phi, double& theta, double& dphi) {
+// With robots, rb holds the lane's mass, L^-1, mu and R across the trial loop; the weights are
+// read here from the robot's row of Q or Qf.
+template <bool PLAN, bool ROBOT>
+__device__ void stage_merit(const Model& m, const LsArgsT<PLAN, ROBOT>& a, const RobotVals<ROBOT>& rb, int qp,
+                            int k, double al, bool grad, double& phi, double& theta, double& dphi) {
   const srbd_model_params& p = m.p;
   const int N = a.N;
   const double* x = a.xs + ((size_t)qp * (N + 1) + k) * 12;
@@ -395,8 +435,13 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN>& a, int qp, int 
   #pragma unroll
   for (int i = 0; i < 12; ++i) {
     const double e = xa[i] - x_ref_at<PLAN>(p, a, ((size_t)qp * (N + 1) + k) * 12 + i, i);
-    phi += 0.5 * sc * w[i] * e * e;
-    if (grad) dphi += dx[i] * sc * w[i] * e;
+    double wi;
+    if constexpr (ROBOT)
+      wi = rb.w(p, k == N, i);
+    else
+      wi = w[i];
+    phi += 0.5 * sc * wi * e * e;
+    if (grad) dphi += dx[i] * sc * wi * e;
   }
   if (k == N) return;
   const double* u = a.us + ((size_t)qp * N + k) * 12;
@@ -417,7 +462,7 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN>& a, int qp, int 
   }
 #pragma unroll 1
   for (int s = 0; s < 4; ++s) {
-    m.f(sv, xt, ua, kk);
+    m.f(sv, rb, xt, ua, kk);
     const double wt = (s == 0 || s == 3) ? 1.0 : 2.0;
     const double h = s < 2 ? 0.5 * dt : dt;
     #pragma unroll
@@ -434,12 +479,12 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN>& a, int qp, int 
   }
   // input cost: relaxed barrier of the friction cone + 0.5 u'R u
   double v[24];
-  cone_rows(p, sv, ua, v);
+  cone_rows(p, sv, rb.mu(p), ua, v);
   double ju[12], db[24];
   #pragma unroll
   for (int i = 0; i < 12; ++i) {
-    ju[i] = p.R * ua[i];
-    phi += 0.5 * p.R * ua[i] * ua[i];
+    ju[i] = rb.R(p) * ua[i];
+    phi += 0.5 * rb.R(p) * ua[i] * ua[i];
   }
   #pragma unroll
   for (int c = 0; c < 24; ++c) {
@@ -454,24 +499,27 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN>& a, int qp, int 
     }
   }
   if (grad) {
-    cone_grad(p, db, ju);
+    cone_grad(p, rb.mu(p), db, ju);
     #pragma unroll
     for (int i = 0; i < 12; ++i) dphi += du[i] * ju[i];
   }
 }
 
 // With a plan, lane l reads the plan rows of its own stages l, l + 32, ...
-template <bool PLAN>
-__global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PLAN> a) {
+// With robots, every lane of the group loads its robot's scalars once, before the loops.
+template <bool PLAN, bool ROBOT>
+__global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PLAN, ROBOT> a) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int qp = gid / kLsGroup, lane = gid % kLsGroup;
   if (qp >= a.batch) return;
   if (a.done && a.done[qp]) return;  // group-uniform
   const int N = a.N;
   const srbd_linesearch_params& ls = a.ls;
+  const RobotVals<ROBOT> rb = load_robot<ROBOT>(m.p, a, (size_t)qp);
   // merit at the current iterate
   double phi = 0.0, theta = 0.0, dphi = 0.0;
-  for (int k = lane; k <= N; k += kLsGroup) stage_merit<PLAN>(m, a, qp, k, 0.0, true, phi, theta, dphi);
+  for (int k = lane; k <= N; k += kLsGroup)
+    stage_merit<PLAN, ROBOT>(m, a, rb, qp, k, 0.0, true, phi, theta, dphi);
   phi = gsum32(phi);
   theta = gsum32(theta);
   dphi = gsum32(dphi);
@@ -479,7 +527,8 @@ __global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PL
   double accepted = -1.0;  // accepted step length, -1: none
   while (alpha > ls.alpha_min) {
     double pa = 0.0, ta = 0.0, unused = 0.0;
-    for (int k = lane; k <= N; k += kLsGroup) stage_merit<PLAN>(m, a, qp, k, alpha, false, pa, ta, unused);
+    for (int k = lane; k <= N; k += kLsGroup)
+      stage_merit<PLAN, ROBOT>(m, a, rb, qp, k, alpha, false, pa, ta, unused);
     pa = gsum32(pa);
     ta = gsum32(ta);
     bool ok;
@@ -523,29 +572,47 @@ __global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PL
 bool plan_given(const srbd_plan_f64* plan) {
   return plan && (plan->x_ref || plan->foot_r || plan->foot_l || plan->fz_max);
 }
+// and the ROBOT kernels only when the MODEL role overrides something
+bool robots_given(const srbd_robots_f64* rb) {
+  return rb && (rb->mass || rb->Lbody || rb->mu || rb->Q || rb->Qf || rb->R);
+}
+// Fill the kernel's argument block from its three parts and launch the (PLAN, ROBOT) instantiation.
+template <bool PLAN, bool ROBOT, class Base, class Launch>
+void with_args(const Base& a, const srbd_plan_f64* plan, const srbd_robots_f64* robots, Launch&& launch) {
+  std::conditional_t<std::is_same_v<Base, LinArgs>, LinArgsT<PLAN, ROBOT>, LsArgsT<PLAN, ROBOT>> full;
+  static_cast<Base&>(full) = a;
+  if constexpr (PLAN) static_cast<srbd_plan_f64&>(full) = *plan;
+  if constexpr (ROBOT) static_cast<srbd_robots_f64&>(full) = *robots;
+  launch(full);
+}
+// the four instantiations: fn is called with std::bool_constant<PLAN>, std::bool_constant<ROBOT>
+template <class Fn>
+void dispatch(bool plan, bool robot, Fn&& fn) {
+  if (plan && robot) fn(std::true_type{}, std::true_type{});
+  else if (plan) fn(std::true_type{}, std::false_type{});
+  else if (robot) fn(std::false_type{}, std::true_type{});
+  else fn(std::false_type{}, std::false_type{});
+}
 
 }  // namespace
 
 hipError_t launch_srbd_linesearch(const srbd_model_params& p, const srbd_linesearch_params& ls,
                                   int batch, int N, double* xs, double* us, const double* dx,
                                   const double* du, double* alpha, double* merit, int* converged,
-                                  hipStream_t stream, const int* done, const srbd_plan_f64* plan) {
+                                  hipStream_t stream, const int* done, const srbd_plan_f64* plan,
+                                  const srbd_robots_f64* robots) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
   const LsArgs a{batch, N, xs, us, dx, du, alpha, merit, converged, ls, p.qf_scale, done};
   const long long n = (long long)batch * kLsGroup;
   const int threads = 64;
   const dim3 grid((unsigned)((n + threads - 1) / threads));
-  if (plan_given(plan)) {
-    LsArgsT<true> ap;
-    static_cast<LsArgs&>(ap) = a;
-    static_cast<srbd_plan_f64&>(ap) = *plan;
-    hipLaunchKernelGGL(srbd_linesearch_kernel<true>, grid, dim3(threads), 0, stream, m, ap);
-  } else {
-    LsArgsT<false> an;
-    static_cast<LsArgs&>(an) = a;
-    hipLaunchKernelGGL(srbd_linesearch_kernel<false>, grid, dim3(threads), 0, stream, m, an);
-  }
+  dispatch(plan_given(plan), robots_given(robots), [&](auto PL, auto RB) {
+    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value;
+    with_args<kP, kR>(a, plan, robots, [&](const auto& full) {
+      hipLaunchKernelGGL((srbd_linesearch_kernel<kP, kR>), grid, dim3(threads), 0, stream, m, full);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -607,7 +674,7 @@ hipError_t launch_nmpc_after(int batch, int it, const int* conv, int* done, int*
 hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, int mode,
                                  const double* xs, const double* us,
                                  const srbd_qp_data_f64& out, hipStream_t stream,
-                                 const srbd_plan_f64* plan) {
+                                 const srbd_plan_f64* plan, const srbd_robots_f64* robots) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
   const LinArgs a{batch, N, mode, xs, us, out, p.qf_scale};
@@ -619,18 +686,14 @@ hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, i
   const long long nst = (long long)batch * N;
   const long long ncost = (long long)batch * (N + 1) * (72 + 12) + (mode == 2 ? (long long)batch * 24 : 0);
   const dim3 gstage((unsigned)((nst + kLinThreads - 1) / kLinThreads)), gcost((unsigned)((ncost + 255) / 256));
-  if (plan_given(plan)) {
-    LinArgsT<true> ap;
-    static_cast<LinArgs&>(ap) = a;
-    static_cast<srbd_plan_f64&>(ap) = *plan;
-    hipLaunchKernelGGL(srbd_lin_stage_kernel<true>, gstage, dim3(kLinThreads), 0, stream, m, ap);
-    hipLaunchKernelGGL(srbd_lin_cost_kernel<true>, gcost, dim3(256), 0, stream, m, ap);
-  } else {
-    LinArgsT<false> an;
-    static_cast<LinArgs&>(an) = a;
-    hipLaunchKernelGGL(srbd_lin_stage_kernel<false>, gstage, dim3(kLinThreads), 0, stream, m, an);
-    hipLaunchKernelGGL(srbd_lin_cost_kernel<false>, gcost, dim3(256), 0, stream, m, an);
-  }
+  dispatch(plan_given(plan), robots_given(robots), [&](auto PL, auto RB) {
+    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value;
+    with_args<kP, kR>(a, plan, robots, [&](const auto& full) {
+      hipLaunchKernelGGL((srbd_lin_stage_kernel<kP, kR>), gstage, dim3(kLinThreads), 0, stream, m,
+                         full);
+      hipLaunchKernelGGL((srbd_lin_cost_kernel<kP, kR>), gcost, dim3(256), 0, stream, m, full);
+    });
+  });
   return hipGetLastError();
 }
 

@@ -163,17 +163,71 @@ __device__ __forceinline__ double x_ref_at(const srbd_model_params& p, const Pla
   return p.x_ref[i];
 }
 
+// Robots (srbd_robots_f64) override six more constants per robot, not per stage: the mass,
+// the body inertia, the friction coefficient and the weights Q, Qf, R.  Kernels and helpers
+// that read them take a `bool ROBOT` beside PLAN: false is the code without robots (the values
+// are Model::p's, RobotVals is empty), true loads them from the robots' arrays, a NULL array
+// falling back to Model::p on a wave-uniform branch.
+struct NoRobots {};
+template <bool ROBOT>
+using RobotArgs = std::conditional_t<ROBOT, srbd_robots_f64, NoRobots>;
+
+// The constants of one robot.  With robots, the mass, L^-1, mu and R are loaded once per
+// thread and stay in registers; the 24 weights are read from the robot's rows (96 bytes each,
+// cache-resident) where they are used: they would double a lane's live state.
+template <bool ROBOT>
+struct RobotVals {
+  __device__ __forceinline__ double mass(const srbd_model_params& p) const { return p.mass; }
+  __device__ __forceinline__ double inv_L(const srbd_model_params& p, int i) const { return 1.0 / p.Lbody[i]; }
+  __device__ __forceinline__ double mu(const srbd_model_params& p) const { return p.mu; }
+  __device__ __forceinline__ double R(const srbd_model_params& p) const { return p.R; }
+  // weight i of the stage cost (k < N) or of the terminal cost
+  __device__ __forceinline__ double w(const srbd_model_params& p, bool terminal, int i) const {
+    return terminal ? p.Qf[i] : p.Q[i];
+  }
+};
+template <>
+struct RobotVals<true> {
+  double m, iL[3], mu_, R_;
+  const double *Q, *Qf;  // the robot's rows, or NULL
+  __device__ __forceinline__ double mass(const srbd_model_params&) const { return m; }
+  __device__ __forceinline__ double inv_L(const srbd_model_params&, int i) const { return iL[i]; }
+  __device__ __forceinline__ double mu(const srbd_model_params&) const { return mu_; }
+  __device__ __forceinline__ double R(const srbd_model_params&) const { return R_; }
+  __device__ __forceinline__ double w(const srbd_model_params& p, bool terminal, int i) const {
+    if (terminal) return Qf ? Qf[i] : p.Qf[i];
+    return Q ? Q[i] : p.Q[i];
+  }
+};
+// rows qp of mass, mu, R ([batch]), Lbody ([batch][3]) and Q, Qf ([batch][12])
+template <bool ROBOT>
+__device__ __forceinline__ RobotVals<ROBOT> load_robot(const srbd_model_params& p, const RobotArgs<ROBOT>& rb,
+                                                       size_t qp) {
+  RobotVals<ROBOT> r;
+  if constexpr (ROBOT) {
+    r.m = rb.mass ? rb.mass[qp] : p.mass;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r.iL[i] = 1.0 / (rb.Lbody ? rb.Lbody[qp * 3 + i] : p.Lbody[i]);
+    r.mu_ = rb.mu ? rb.mu[qp] : p.mu;
+    r.R_ = rb.R ? rb.R[qp] : p.R;
+    r.Q = rb.Q ? rb.Q + qp * 12 : nullptr;
+    r.Qf = rb.Qf ? rb.Qf + qp * 12 : nullptr;
+  }
+  return r;
+}
+
 struct Model {
   srbd_model_params p;
-  __device__ double ac(int c, int j) const {
+  // friction coefficient mu: p.mu, or the robot's
+  __device__ double ac(int c, int j, double mu) const {
     // friction cone / torque rows of one leg (SRBD_model.cpp:237-260), R_f = I
     const int leg = c / 12, r = c % 12, jj = j - 6 * leg;
     if (jj < 0 || jj >= 6) return 0.0;
     switch (r) {
-      case 0: return jj == 0 ? -1.0 : (jj == 2 ? p.mu : 0.0);
-      case 1: return jj == 1 ? -1.0 : (jj == 2 ? p.mu : 0.0);
-      case 2: return jj == 0 ? 1.0 : (jj == 2 ? p.mu : 0.0);
-      case 3: return jj == 1 ? 1.0 : (jj == 2 ? p.mu : 0.0);
+      case 0: return jj == 0 ? -1.0 : (jj == 2 ? mu : 0.0);
+      case 1: return jj == 1 ? -1.0 : (jj == 2 ? mu : 0.0);
+      case 2: return jj == 0 ? 1.0 : (jj == 2 ? mu : 0.0);
+      case 3: return jj == 1 ? 1.0 : (jj == 2 ? mu : 0.0);
       case 4: return jj == 2 ? -1.0 : 0.0;
       case 5: return jj == 2 ? 1.0 : 0.0;
       case 6: return jj == 2 ? p.Lfx : (jj == 4 ? -1.0 : 0.0);
@@ -189,13 +243,13 @@ struct Model {
     return r == 4 ? p.fmax : (r == 5 ? -p.fmin : 0.0);
   }
   // continuous dynamics f(x, u) (GetContinuousDynamic)
-  template <class St>
-  __device__ void f(const St& s, const double* x, const double* u, double* dx) const {
+  template <class St, class Rb>
+  __device__ void f(const St& s, const Rb& rb, const double* x, const double* u, double* dx) const {
     const V3 r = seg(x, 0), l = seg(x, 3), pos = seg(x, 6);
     const M3 R = expm(r), Jlt = jlt(r);
     const M3 Lb = [&] {
       M3 m = zero3();
-      for (int i = 0; i < 3; ++i) m.a[i][i] = 1.0 / p.Lbody[i];  // SetInertia stores L^-1
+      for (int i = 0; i < 3; ++i) m.a[i][i] = rb.inv_L(p, i);  // SetInertia stores L^-1
       return m;
     }();
     const M3 RLR = mul(mul(R, Lb), tr(R));
@@ -208,20 +262,20 @@ struct Model {
       dx[i] = dr.v[i];
       dx[3 + i] = u[3 + i] + u[9 + i] + t0.v[i] + t1.v[i];
       dx[6 + i] = x[9 + i];
-      dx[9 + i] = (u[i] + u[6 + i]) / p.mass + (i == 2 ? -9.8 : 0.0);
+      dx[9 + i] = (u[i] + u[6 + i]) / rb.mass(p) + (i == 2 ? -9.8 : 0.0);
     }
   }
   // Jacobian blocks of f (the nonzero 3x3 blocks of jfx / jfu, :104-176):
   // jfx[0:3,0:3] = J00, jfx[0:3,3:6] = J01, jfx[3:6,6:9] = [f0 + f1]x,
   // jfx[6:9,9:12] = I; jfu[3:6,0:3] = [p0]x, jfu[3:6,6:9] = [p1]x,
   // jfu[3:6,3:6] = jfu[3:6,9:12] = I, jfu[9:12,0:3] = jfu[9:12,6:9] = I / m
-  template <class St>
-  __device__ void jac_blocks(const St& s, const double* x, const double* u, M3& J00, M3& J01, M3& Sf,
-                             M3& S0, M3& S1) const {
+  template <class St, class Rb>
+  __device__ void jac_blocks(const St& s, const Rb& rb, const double* x, const double* u, M3& J00, M3& J01,
+                             M3& Sf, M3& S0, M3& S1) const {
     const V3 r = seg(x, 0), l = seg(x, 3), pos = seg(x, 6);
     const M3 R = expm(r), Jlt = jlt(r);
     M3 Lb = zero3();
-    for (int i = 0; i < 3; ++i) Lb.a[i][i] = 1.0 / p.Lbody[i];
+    for (int i = 0; i < 3; ++i) Lb.a[i][i] = rb.inv_L(p, i);
     const M3 RLR = mul(mul(R, Lb), tr(R));
     const V3 w = mv(RLR, l);
     const M3 mid = mul(mul(Jlt, add(mul(RLR, skew(l)), lin(-1.0, skew(w), 0.0, Lb))), jl(r));

@@ -98,6 +98,8 @@ struct srbd_qp_handle_s {
   // srbd_qp_srbd_rollout_f64: the step's sqp_iter / converged (capacity ints each), and the
   // dense plan window of one tick (first rollout with a plan)
   srbd::Buffer roll, roll_plan;
+  // srbd_qp_srbd_set_robots_f64: the two roles' pointers (the caller's arrays; all NULL = clear)
+  srbd_robots_f64 robots_model{}, robots_plant{};
   // settings.f64_rescue: the compact fp64 batch, and that of the cold fp64 re-solve of
   // rescued QPs the continuation left unsolved
   srbd::Buffer resc, resc2;
@@ -1332,7 +1334,20 @@ void srbd_qp_srbd_default_params(srbd_model_params* p) {
   p->qf_scale = 0.0;  // N
 }
 
+int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f64* robots) {
+  if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
+  if (role != SRBD_QP_ROBOTS_MODEL && role != SRBD_QP_ROBOTS_PLANT)
+    return fail(SRBD_QP_EINVAL, "set_robots: unknown role " + std::to_string(role));
+  if (h->dims.nx != 12 || h->dims.nu != 12) return fail(SRBD_QP_EDIM, "SRBD robots need nx = nu = 12");
+  const srbd_robots_f64 r = robots ? *robots : srbd_robots_f64{};
+  if (role == SRBD_QP_ROBOTS_PLANT && (r.mu || r.Q || r.Qf || r.R))
+    return fail(SRBD_QP_EINVAL, "set_robots: the PLANT role takes mass and Lbody only");
+  (role == SRBD_QP_ROBOTS_MODEL ? h->robots_model : h->robots_plant) = r;
+  return SRBD_QP_OK;
+}
+
 // The _plan_ entry points hold the checks and the work; the plain ones forward a NULL plan.
+// All of them read the handle's robots (srbd_qp_srbd_set_robots_f64).
 int srbd_qp_srbd_linearize_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
                                     const srbd_plan_f64* plan, int constraints, const double* xs,
                                     const double* us, const srbd_qp_data_f64* out, void* stream) {
@@ -1353,7 +1368,8 @@ int srbd_qp_srbd_linearize_plan_f64(srbd_qp_handle h, int batch, const srbd_mode
   if (p.qf_scale <= 0.0) p.qf_scale = (double)d.N;
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
   srbd::DeviceGuard guard(h->device);
-  const hipError_t e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, *out, strm, plan);
+  const hipError_t e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, *out, strm, plan,
+                                                   &h->robots_model);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1390,7 +1406,7 @@ int srbd_qp_srbd_linesearch_plan_f64(srbd_qp_handle h, int batch, const srbd_mod
   hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
   srbd::DeviceGuard guard(h->device);
   const hipError_t e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, dx, du, alpha,
-                                                    merit, converged, strm, nullptr, plan);
+                                                    merit, converged, strm, nullptr, plan, &h->robots_model);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1461,14 +1477,14 @@ int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_par
   if (p.qf_scale <= 0.0) p.qf_scale = (double)d.N;
   // NMPC_solver.cpp:362-372: prepareQpStructures; solveQpProblems; if (checkConvergence()) break;
   for (int it = 0; it < sqp_max_loop && e == hipSuccess; ++it) {
-    e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, qd, strm, plan);
+    e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, qd, strm, plan, &h->robots_model);
     if (e == hipSuccess)
       e = srbd::launch_nmpc_prep(batch, d.N, it, xs, x0, at(bx0), done, sqp_iter, converged, strm);
     if (e != hipSuccess) break;
     rc = solve_impl<double>(h, batch, settings, &qd, &sol, strm);
     if (rc) return rc;
     e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, at(bx), at(bu), alpha, nullptr,
-                                     conv, strm, done, plan);
+                                     conv, strm, done, plan, &h->robots_model);
     if (e == hipSuccess)
       e = srbd::launch_nmpc_after(batch, it, conv, done, sqp_iter, converged, active, strm);
     if (e == hipSuccess)
@@ -1514,7 +1530,8 @@ int srbd_qp_srbd_advance_f64(srbd_qp_handle h, int batch, const srbd_model_param
   io.wrench_stride = 6;
   io.u_out = u_applied;
   io.u_stride = 12;
-  const hipError_t e = srbd::launch_srbd_advance(*params, batch, d.N, io, plan, strm);
+  const hipError_t e = srbd::launch_srbd_advance(*params, batch, d.N, io, plan, strm, &h->robots_model,
+                                                 &h->robots_plant);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1635,7 +1652,7 @@ int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_param
     io.it_log = roll->sqp_iter_log ? roll->sqp_iter_log + t : nullptr;
     io.cv_log = roll->converged_log ? roll->converged_log + t : nullptr;
     io.log_stride = T;
-    e = srbd::launch_srbd_advance(*params, batch, N, io, wplan, strm);
+    e = srbd::launch_srbd_advance(*params, batch, N, io, wplan, strm, &h->robots_model, &h->robots_plant);
     if (e != hipSuccess) return device_error(e, "rollout: ");
   }
   e = hipStreamSynchronize(strm);

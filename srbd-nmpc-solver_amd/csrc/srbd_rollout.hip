@@ -32,18 +32,27 @@ struct AdvArgs {
   int *it_log, *cv_log;
   long long log_stride;
 };
-template <bool PLAN>
-struct AdvArgsT : AdvArgs, PlanArgs<PLAN> {};
+// With robots: what the two lanes that run the model read of the handle's roles, the mass
+// and the inertia.  The launcher has resolved the plant's fallback to the MODEL role per field;
+// a field that is still NULL is Model::p's.
+struct AdvRobots {
+  const double *model_mass, *model_Lbody;  // lane 1
+  const double *plant_mass, *plant_Lbody;  // lane 0
+};
+struct NoAdvRobots {};
+template <bool PLAN, bool ROBOT>
+struct AdvArgsT : AdvArgs, PlanArgs<PLAN>, std::conditional_t<ROBOT, AdvRobots, NoAdvRobots> {};
 
 // `steps` classical RK4 steps of length h of xdot = f(x, u) + w from x (in place).  With has_w,
 // w adds wr[0:3] to rows 3..5 and wr[3:6] / mass to rows 9..11 of every slope.  The slopes
 // go through one call site of the model, as in the line search's stage_merit.
-template <class St>
-__device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, double (&x)[12], const double (&u)[12],
-                                          const double (&wr)[6], bool has_w, double h, int steps) {
+template <class St, class Rb>
+__device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, const Rb& rb, double (&x)[12],
+                                          const double (&u)[12], const double (&wr)[6], bool has_w, double h,
+                                          int steps) {
   double fw[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) fw[i] = wr[3 + i] / m.p.mass;
+  for (int i = 0; i < 3; ++i) fw[i] = wr[3 + i] / rb.mass(m.p);
 #pragma unroll 1
   for (int st = 0; st < steps; ++st) {
     double acc[12], xt[12], kk[12];
@@ -54,7 +63,7 @@ __device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, double (
     }
 #pragma unroll 1
     for (int s = 0; s < 4; ++s) {
-      m.f(sv, xt, u, kk);
+      m.f(sv, rb, xt, u, kk);
       if (has_w) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -79,7 +88,9 @@ __device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, double (
 //   Lane 0 is the plant: u0 = us[0] (also written to u_out), x <- `substeps` RK4 steps of
 //   dt / substeps with u0, the wrench and stage 0's feet.  Lane 1 is the new last stage:
 //   xN = one RK4 step over dt from xs[N] with us[N-1] and stage N-1's feet, no wrench.  Both
-//   run the same code on their own inputs.
+//   run the same code on their own inputs.  With robots, lane 0 integrates the true robot
+//   (the PLANT role's mass and inertia, else the MODEL role's, else Model::p's) and lane 1 the
+//   robot the controller believes in (the MODEL role's).
 //   Then the whole wave shifts the robot's rows by one stage (12 doubles = 6 double2), in place:
 //   xs[k] <- xs[k+1] (k < N), us[k] <- us[k+1] (k < N-1), and lane 1 stores xN to xs[N].
 //
@@ -97,8 +108,8 @@ __device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, double (
 // instructions.
 // Rows are multiples of 96 bytes and the shift is 96 bytes, so the double2 accesses stay 16-byte
 // aligned (the entry point checks the base pointers), adjacent lanes on adjacent 16 bytes.
-template <bool PLAN>
-__global__ void __launch_bounds__(kWave* kAdvWaves) srbd_advance_kernel(Model m, AdvArgsT<PLAN> a) {
+template <bool PLAN, bool ROBOT>
+__global__ void __launch_bounds__(kWave* kAdvWaves) srbd_advance_kernel(Model m, AdvArgsT<PLAN, ROBOT> a) {
   const int lane = threadIdx.x & (kWave - 1);
   const long long qp = (long long)blockIdx.x * kAdvWaves + (threadIdx.x >> 6);
   if (qp >= a.batch) return;  // wave-uniform
@@ -119,6 +130,12 @@ __global__ void __launch_bounds__(kWave* kAdvWaves) srbd_advance_kernel(Model m,
 #pragma unroll
       for (int i = 0; i < 12; ++i) xv[i] = xin[i];
       const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)qp * N + k);
+      RobotArgs<ROBOT> role{};
+      if constexpr (ROBOT) {
+        role.mass = plant ? a.plant_mass : a.model_mass;
+        role.Lbody = plant ? a.plant_Lbody : a.model_Lbody;
+      }
+      const RobotVals<ROBOT> rb = load_robot<ROBOT>(p, role, (size_t)qp);
       double wr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       const bool has_w = plant && a.wrench != nullptr;
       if (has_w) {
@@ -126,7 +143,7 @@ __global__ void __launch_bounds__(kWave* kAdvWaves) srbd_advance_kernel(Model m,
         for (int i = 0; i < 6; ++i) wr[i] = a.wrench[(size_t)qp * a.wrench_stride + i];
       }
       const int steps = plant ? a.substeps : 1;
-      rk4_steps(m, sv, xv, u, wr, has_w, p.dt / (double)steps, steps);
+      rk4_steps(m, sv, rb, xv, u, wr, has_w, p.dt / (double)steps, steps);
     }
     if (plant) {
       if (a.u_out) {
@@ -207,7 +224,8 @@ __global__ void __launch_bounds__(256) rollout_rows_kernel(RowsArgs a) {
 }  // namespace
 
 hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, const AdvanceIo& io,
-                               const srbd_plan_f64* plan, hipStream_t stream) {
+                               const srbd_plan_f64* plan, hipStream_t stream, const srbd_robots_f64* robots,
+                               const srbd_robots_f64* plant) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
   AdvArgs a{};
@@ -229,17 +247,29 @@ hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, con
   a.cv_log = io.cv_log;
   a.log_stride = io.log_stride;
   const dim3 grid((unsigned)((batch + kAdvWaves - 1) / kAdvWaves)), block(kWave * kAdvWaves);
-  // the kernel reads the feet only: a plan without them is the plan-less kernel
-  if (plan && (plan->foot_r || plan->foot_l)) {
-    AdvArgsT<true> ap;
-    static_cast<AdvArgs&>(ap) = a;
-    static_cast<srbd_plan_f64&>(ap) = *plan;
-    hipLaunchKernelGGL(srbd_advance_kernel<true>, grid, block, 0, stream, m, ap);
-  } else {
-    AdvArgsT<false> an;
-    static_cast<AdvArgs&>(an) = a;
-    hipLaunchKernelGGL(srbd_advance_kernel<false>, grid, block, 0, stream, m, an);
+  // the kernel reads the feet only: a plan without them is the plan-less kernel; and of the
+  // robots the mass and the inertia only
+  AdvRobots r{};
+  if (robots) {
+    r.model_mass = r.plant_mass = robots->mass;
+    r.model_Lbody = r.plant_Lbody = robots->Lbody;
   }
+  if (plant && plant->mass) r.plant_mass = plant->mass;
+  if (plant && plant->Lbody) r.plant_Lbody = plant->Lbody;
+  const bool with_plan = plan && (plan->foot_r || plan->foot_l);
+  const bool with_robots = r.model_mass || r.model_Lbody || r.plant_mass || r.plant_Lbody;
+  auto launch = [&](auto PL, auto RB) {
+    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value;
+    AdvArgsT<kP, kR> full;
+    static_cast<AdvArgs&>(full) = a;
+    if constexpr (kP) static_cast<srbd_plan_f64&>(full) = *plan;
+    if constexpr (kR) static_cast<AdvRobots&>(full) = r;
+    hipLaunchKernelGGL((srbd_advance_kernel<kP, kR>), grid, block, 0, stream, m, full);
+  };
+  if (with_plan && with_robots) launch(std::true_type{}, std::true_type{});
+  else if (with_plan) launch(std::true_type{}, std::false_type{});
+  else if (with_robots) launch(std::false_type{}, std::true_type{});
+  else launch(std::false_type{}, std::false_type{});
   return hipGetLastError();
 }
 
