@@ -34,6 +34,9 @@
  *   srbd_qp_srbd_rollout_f64     T ticks of the closed receding-horizon loop around the step.
  *   srbd_qp_srbd_set_robots_f64  per-robot mass, inertia, friction and weights for all of the
  *                                above: what the controller believes, and the true robot.
+ *   srbd_qp_srbd_gait_plan_f64   the producer of a tick's plan: a velocity command, a gait and
+ *                                the measured state in, the window out (Raibert footholds).
+ *   srbd_qp_srbd_rollout_gait_f64  the rollout that replans every tick.
  *
  * ------------------------------------------------------------------------
  * Problem (per QP, stages k = 0..N), identical to hpipm::OcpQp
@@ -612,6 +615,86 @@ typedef struct srbd_robots_f64 { /* device memory, fp64, dense; NULL field = the
 } srbd_robots_f64;
 enum { SRBD_QP_ROBOTS_MODEL = 0, SRBD_QP_ROBOTS_PLANT = 1 };
 int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f64* robots);
+
+/* ------------------------------------------------------------------------
+ * Gait planner (additive to ABI 12): the producer of a tick's plan window.  From a per-robot
+ * velocity command, a per-robot gait (period, swing length and phase offset of each foot, in
+ * stages) and the measured state it writes the window the step and the advance read
+ * (srbd_plan_f64's four arrays for the handle's N), with Raibert foothold feedback: a swinging
+ * foot's touchdown point follows the measured position and velocity until it lands.
+ * Write (vx, vy, wz, zh) for the command, c = x[6:8], vm = x[9:11], dt = params->dt, Rz(a) for
+ * the 2 x 2 rotation and (px, py, yaw) = ref_pose.  Per robot:
+ *   Reference, k = 0..N:  yaw_k = yaw + k (dt wz);  p_0 = anchor ? c : (px, py),
+ *     p_{k+1} = p_k + dt Rz(yaw_k)(vx, vy);
+ *     x_ref[k] = (0, 0, yaw_k, 0, 0, Lz wz, p_k.x, p_k.y, zh, Rz(yaw_k)(vx, vy), 0), Lz the
+ *     MODEL role's Lbody[2] where set (srbd_qp_srbd_set_robots_f64), else params->Lbody[2].
+ *   Contact schedule, k = 0..N-1, foot f (0 right, 1 left), exact 64-bit integers:
+ *     phi = (tick + k + offset_f) mod period; the foot swings at stage k iff phi < swing_f;
+ *     fz_max[k][f] = swing ? fz_swing : fz_stance.
+ *   Foothold of a touchdown at window stage j, with j' = min(j, N), S_f = period - swing_f:
+ *     F_f(j).xy = c + (p_j' - p_0) + Rz(yaw_j')(hip_f + (S_f dt / 2)(vx, vy))
+ *                 + k_raibert (vm - Rz(yaw_0)(vx, vy)),   F_f(j).z = ground_z.
+ *   Foot rows: a swing stage k holds F_f(k + swing_f - phi), its next touchdown.  A stance
+ *     stage k has s = k - (phi - swing_f), the first stage of that stance; with swing_f == 0 or
+ *     s <= 0 the foot is already down and the stage holds foot_now[f]; otherwise F_f(s).
+ *   State: foot_now[f] becomes row 0 of that foot's plan (a stance foot keeps its bits, a
+ *     swinging foot's target follows the measured state until touchdown and is latched from
+ *     then on); ref_pose becomes (p_1, yaw_1).
+ * One call is one tick's planning step: issue it once per tick.  Asynchronous on `stream`
+ * (NULL = the handle's own); all memory is device memory; the window's arrays must not
+ * overlap the inputs.
+ * Caller's contract (device data, not checked): the values of the _r arrays, in the ranges
+ * the scalar fields are checked for.
+ * Checks: a NULL pointer other than the three _r arrays, tick < 0, and, where the _r array is
+ * NULL, period < 1, swing[f] outside [0, period) or offset[f] < 0 are SRBD_QP_EINVAL; so are
+ * fz_swing <= 0 and fz_stance <= fz_swing; the handle needs nx = nu = 12 (SRBD_QP_EDIM);
+ * batch above the capacity is SRBD_QP_ECAPACITY; batch == 0 returns SRBD_QP_OK.
+ * Not per robot (out of scope): hip, the gains, fz_stance / fz_swing; terrain height and
+ * swing-foot trajectories (the model has no foot states).
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_gait_f64 {
+  int period, swing[2], offset[2];  /* in stages; every robot's where the arrays below are NULL */
+  const int* period_r;              /* [batch]     device, optional */
+  const int* swing_r;               /* [batch][2]  (right, left)    */
+  const int* offset_r;              /* [batch][2]                   */
+  double hip[2][2];                 /* (right, left) x (x, y): nominal foothold relative to the body, heading frame */
+  double ground_z, k_raibert;       /* foothold height; velocity-error gain (s) */
+  double fz_stance, fz_swing;       /* fz_max of a stance / swing stage; fz_swing small and positive */
+  int anchor;                       /* 0: the carried reference position; 1: restart it from the measured xy each tick */
+} srbd_gait_f64;
+
+int srbd_qp_srbd_gait_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                               const srbd_gait_f64* gait,
+                               const double* cmd,      /* [batch][4]  vx, vy (heading frame), wz, body height */
+                               const double* x,        /* [batch][12] measured state */
+                               long long tick,
+                               double* ref_pose,       /* [batch][3]  px, py, yaw: in/out */
+                               double* foot_now,       /* [batch][2][3] where each foot stands or is heading: in/out */
+                               double* x_ref, double* foot_r, double* foot_l, double* fz_max,  /* the window, out */
+                               void* stream);
+
+typedef struct srbd_rollout_gait_f64 {
+  const double* cmd;     /* [batch][T][4]  the command of every tick (may be NULL when T == 0) */
+  double* ref_pose;      /* [batch][3]     in/out, as srbd_qp_srbd_gait_plan_f64            */
+  double* foot_now;      /* [batch][2][3]  in/out                                           */
+  long long tick0;       /* tick t plans with tick0 + t; >= 0                               */
+  double* foot_log;      /* [batch][T][2][3] optional: row 0 of each tick's feet            */
+  double* fz_log;        /* [batch][T][2]    optional: row 0 of each tick's fz_max          */
+} srbd_rollout_gait_f64;
+
+/* srbd_qp_srbd_rollout_f64 that replans every tick: the plan is replaced by the gait and its
+ * io.  For t = 0..T-1: (1) the planner runs with cmd[:, t], the current x and tick0 + t and
+ * writes W_t into the handle's plan-window scratch (the buffer of a rollout with a full plan,
+ * the same size); (2)-(6) are srbd_qp_srbd_rollout_f64's, with foot_log[:, t] / fz_log[:, t] =
+ * row 0 of W_t among the logs.  roll->plan_stages is ignored.  The results are the bits of a
+ * caller's loop over srbd_qp_srbd_gait_plan_f64, srbd_qp_srbd_nmpc_plan_f64 and
+ * srbd_qp_srbd_advance_f64.  Checks: the planner's and the rollout's; ticks == 0 or
+ * batch == 0 plan nothing.  A failed check leaves every array as it was.               */
+int srbd_qp_srbd_rollout_gait_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                  const srbd_gait_f64* gait, const srbd_rollout_gait_f64* gio,
+                                  const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
+                                  int constraints, int sqp_max_loop, const srbd_rollout_f64* roll,
+                                  double* xs, double* us, double* x, double* alpha);
 
 /* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,

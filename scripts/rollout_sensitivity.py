@@ -19,6 +19,12 @@ seed + 200, two plant substeps, through robots_host.closed_loop; and how far the
 x_log (the same loop with plant = model).
 
     python scripts/rollout_sensitivity.py --robots --seed 30
+
+With --gait the same for tests/test_gpu_gait.py's replanning rollout: the inputs
+of gait_host.walking_case through gait_host.closed_loop, which plans every tick from the
+measured state, so the perturbation of x reaches the later windows through the feedback.
+
+    python scripts/rollout_sensitivity.py --gait --seed 30
 """
 import argparse
 import sys
@@ -30,6 +36,7 @@ REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO / "tests"))
 sys.path.insert(0, str(REPO / "oracle"))
 
+import gait_host as GH  # noqa: E402
 import helpers  # noqa: E402
 import robots_host as BH  # noqa: E402
 import rollout_host as RH  # noqa: E402
@@ -42,9 +49,14 @@ B, N, T = 4, 10, 4
 
 
 ROBOTS = None  # --robots: (model list, plant list)
+GAIT = False   # --gait: the inputs are gait_host.walking_case's
 
 
 def run(sm, oracle, p, case, inputs):
+    if GAIT:
+        xs, us, x, alpha, gait, cmd, ref_pose, foot_now = inputs
+        return GH.closed_loop(sm, oracle, p, gait, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, 15,
+                              case[0], alpha_reset=case[1])
     xs, us, x, alpha, plan = inputs
     if ROBOTS:
         return BH.closed_loop(sm, oracle, ROBOTS[0], ROBOTS[1], plan, xs, us, x, alpha, T, NMPC, 15, case[0],
@@ -53,7 +65,7 @@ def run(sm, oracle, p, case, inputs):
 
 
 def conditions(sm, oracle, p, seed):
-    inputs = RH.walking_case(sm, p, B, N, T, seed)
+    inputs = (GH if GAIT else RH).walking_case(sm, p, B, N, T, seed)
     out = {}
     for case in CASES:
         h = run(sm, oracle, p, case, inputs)
@@ -62,13 +74,17 @@ def conditions(sm, oracle, p, seed):
 
 
 def main():
-    global ROBOTS
+    global ROBOTS, GAIT
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=30)
     ap.add_argument("--search", type=int, nargs=2, metavar=("FROM", "TO"))
     ap.add_argument("--draws", type=int, default=3)
     ap.add_argument("--robots", action="store_true")
+    ap.add_argument("--gait", action="store_true")
     a = ap.parse_args()
+    if a.gait and a.robots:
+        ap.error("--gait and --robots are separate tables")
+    GAIT = a.gait
     sm, oracle = helpers.load_package().srbd_model, helpers.load_oracle()
     p = sm.SrbdParams()
 
@@ -86,7 +102,7 @@ def main():
         return
     set_robots(a.seed)
     inputs, c = conditions(sm, oracle, p, a.seed)
-    xs, us, x, alpha, plan = inputs
+    xs, us, x = inputs[:3]
     for case in CASES:
         margin, its, base = c[case]
         print(f"{case}: margin {margin:.2e}, sqp iterations {its}\n{base['sqp_iter']}")
@@ -94,7 +110,7 @@ def main():
         for d in range(a.draws):
             rng = np.random.default_rng([a.seed, d])
             pert = lambda v: v * (1.0 + 1e-7 * rng.choice([-1.0, 1.0], size=v.shape))
-            h = run(sm, oracle, p, case, (pert(xs), pert(us), pert(x), alpha, plan))
+            h = run(sm, oracle, p, case, (pert(xs), pert(us), pert(x)) + tuple(inputs[3:]))
             same = np.array_equal(h["sqp_iter"], base["sqp_iter"])
             dx = np.maximum(dx, np.abs(h["x_log"][:, 1:] - base["x_log"][:, 1:]).max(axis=(0, 2)))
             du = np.maximum(du, np.abs(h["u_log"] - base["u_log"]).max(axis=(0, 2)))

@@ -222,6 +222,69 @@ class RolloutStruct(C.Structure):
                 ("converged_log", _dp)]
 
 
+class GaitStruct(C.Structure):
+    """srbd_gait_f64."""
+    _fields_ = [("period", C.c_int), ("swing", C.c_int * 2), ("offset", C.c_int * 2), ("period_r", _dp),
+                ("swing_r", _dp), ("offset_r", _dp), ("hip", (C.c_double * 2) * 2), ("ground_z", C.c_double),
+                ("k_raibert", C.c_double), ("fz_stance", C.c_double), ("fz_swing", C.c_double),
+                ("anchor", C.c_int)]
+
+
+class RolloutGaitStruct(C.Structure):
+    """srbd_rollout_gait_f64."""
+    _fields_ = [("cmd", _dp), ("ref_pose", _dp), ("foot_now", _dp), ("tick0", C.c_longlong),
+                ("foot_log", _dp), ("fz_log", _dp)]
+
+
+class Gait:
+    """A gait for srbd_gait_plan / srbd_rollout_gait (srbd_gait_f64).  period, swing = (right,
+    left) and offset = (right, left) are in stages: ints for every robot, or torch int32 device
+    tensors [B] / [B][2] / [B][2] for per-robot gaits (the struct's _r arrays; their values are
+    the caller's contract).  hip = ((x, y) right, (x, y) left): the nominal foothold relative to
+    the body in the heading frame; ground_z: the foothold height; k_raibert: the velocity-error
+    gain (s); fz_stance / fz_swing: fz_max of a stance / swing stage; anchor: 0 carries the
+    reference position, 1 restarts it from the measured xy every tick.
+    The holder keeps the tensors alive; the calls check dtype, contiguity, shapes and device."""
+    INT_FIELDS = {"period": (), "swing": (2,), "offset": (2,)}
+
+    def __init__(self, period=1, swing=(0, 0), offset=(0, 0), hip=((0.0, -0.1), (0.0, 0.1)),
+                 ground_z=0.0, k_raibert=0.0, fz_stance=1000.0, fz_swing=1.0, anchor=0):
+        self.period, self.swing, self.offset = period, swing, offset
+        self.hip, self.ground_z, self.k_raibert = hip, ground_z, k_raibert
+        self.fz_stance, self.fz_swing, self.anchor = fz_stance, fz_swing, anchor
+
+    def struct(self, B: int, device=None) -> GaitStruct:
+        """The C struct for a batch of B robots; ValueError on a tensor that does not fit."""
+        import torch
+        gs = GaitStruct()
+        for name, tail in self.INT_FIELDS.items():
+            v = getattr(self, name)
+            if isinstance(v, torch.Tensor):
+                want = (int(B),) + tail
+                if v.dtype != torch.int32:
+                    raise ValueError(f"gait.{name} must be a torch.int32 tensor or Python ints")
+                if tuple(v.shape) != want:
+                    raise ValueError(f"gait.{name} has shape {tuple(v.shape)}, expected {want}")
+                if not v.is_contiguous():
+                    raise ValueError(f"gait.{name} must be contiguous")
+                if device is not None and v.device != device:
+                    raise ValueError(f"gait.{name} is on {v.device}, the trajectories on {device}")
+                setattr(gs, name + "_r", v.data_ptr())
+            elif tail:
+                if len(v) != 2:
+                    raise ValueError(f"gait.{name} needs two values (right, left), got {len(v)}")
+                for f in range(2):
+                    getattr(gs, name)[f] = int(v[f])
+            else:
+                gs.period = int(v)
+        for f in range(2):
+            for i in range(2):
+                gs.hip[f][i] = float(self.hip[f][i])
+        gs.ground_z, gs.k_raibert = float(self.ground_z), float(self.k_raibert)
+        gs.fz_stance, gs.fz_swing, gs.anchor = float(self.fz_stance), float(self.fz_swing), int(self.anchor)
+        return gs
+
+
 _lib = None
 
 
@@ -351,6 +414,16 @@ def lib():
         if hasattr(L, "srbd_qp_srbd_set_robots_f64"):  # robots (older builds: A/B runs)
             L.srbd_qp_srbd_set_robots_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(RobotsStruct)]
             L.srbd_qp_srbd_set_robots_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_srbd_gait_plan_f64"):  # the gait planner (older builds: A/B runs)
+            L.srbd_qp_srbd_gait_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                     C.POINTER(GaitStruct), C.c_void_p, C.c_void_p,
+                                                     C.c_longlong] + [C.c_void_p] * 7
+            L.srbd_qp_srbd_gait_plan_f64.restype = C.c_int
+            L.srbd_qp_srbd_rollout_gait_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
+                                                        C.POINTER(GaitStruct), C.POINTER(RolloutGaitStruct),
+                                                        C.POINTER(LsParams), C.POINTER(Settings), C.c_int,
+                                                        C.c_int, C.POINTER(RolloutStruct)] + [C.c_void_p] * 4
+            L.srbd_qp_srbd_rollout_gait_f64.restype = C.c_int
         L.srbd_qp_abi_version.argtypes = []
         L.srbd_qp_abi_version.restype = C.c_int
         _lib = L
@@ -880,3 +953,95 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
           "srbd_qp_srbd_rollout_f64")
     _order_after(o)
     return x_log, u_log, it_log, cv_log
+
+
+def _check_gait_state(B, dev, x, ref_pose, foot_now):
+    _check_f64("x", x, (B, 12), dev)
+    _check_f64("ref_pose", ref_pose, (B, 3), dev)
+    _check_f64("foot_now", foot_now, (B, 2, 3), dev)
+
+
+def srbd_gait_plan(handle: Handle, gait: Gait, cmd, x, tick: int, ref_pose, foot_now,
+                   params: Optional[ModelParams] = None, stream: int = 0, out: Optional[Plan] = None) -> Plan:
+    """One tick's planning step on the device (srbd_qp_srbd_gait_plan_f64): from the command
+    cmd [B][4] (vx, vy in the heading frame, wz, body height), the measured state x [B][12] and
+    `tick`, the plan window of the handle's horizon N under `gait` (a Gait), with Raibert
+    foothold feedback.  ref_pose [B][3] (px, py, yaw) and foot_now [B][2][3] are carried from
+    tick to tick and updated in place: call once per tick.  Torch fp64 device tensors.
+    Asynchronous on the handle's stream, ordered like a torch op.  Returns the window as a Plan
+    (x_ref [B][N+1][12], foot_r / foot_l [B][N][3], fz_max [B][N][2]); `out`: a Plan from an
+    earlier call to write into."""
+    import torch
+    if not isinstance(cmd, torch.Tensor) or cmd.dim() < 1:
+        raise ValueError("cmd must be a torch.float64 tensor")
+    B, dev = cmd.shape[0], cmd.device
+    _check_f64("cmd", cmd, (B, 4), dev)
+    _check_gait_state(B, dev, x, ref_pose, foot_now)
+    gs = gait.struct(B, dev)
+    N = handle.dims.N
+    if out is None:
+        f = dict(dtype=torch.float64, device=dev)
+        out = Plan(torch.empty(B, N + 1, 12, **f), torch.empty(B, N, 3, **f), torch.empty(B, N, 3, **f),
+                   torch.empty(B, N, 2, **f))
+    elif None in (out.x_ref, out.foot_r, out.foot_l, out.fz_max):
+        raise ValueError("out needs all four of x_ref, foot_r, foot_l, fz_max")
+    out.struct(B, N, dev)  # the shapes
+    _check_robots(handle, B)
+    p = params or default_model_params()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    o = _order_before(handle, stream, True)
+    check(lib().srbd_qp_srbd_gait_plan_f64(handle.ptr, int(B), C.byref(p), C.byref(gs), ptr(cmd), ptr(x),
+                                           int(tick), ptr(ref_pose), ptr(foot_now), ptr(out.x_ref),
+                                           ptr(out.foot_r), ptr(out.foot_l), ptr(out.fz_max),
+                                           C.c_void_p(stream or None)), "srbd_qp_srbd_gait_plan_f64")
+    _order_after(o)
+    return out
+
+
+def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pose, foot_now, ticks: int,
+                      tick0: int = 0, constraints: str = "none", settings: Optional[Dict] = None,
+                      sqp_max_loop: int = 15, wrench=None, substeps: int = 1, alpha_reset: float = 0.0,
+                      params: Optional[ModelParams] = None, ls: Optional[LsParams] = None):
+    """srbd_rollout that replans every tick (srbd_qp_srbd_rollout_gait_f64): per tick
+    srbd_gait_plan with cmd[:, t], the current x and tick0 + t, then the NMPC step on that
+    window, then srbd_advance with it and wrench[:, t].  cmd [B][ticks][4]; ref_pose [B][3] and
+    foot_now [B][2][3] are updated in place like xs, us, x, alpha.  Synchronous.  Returns
+    (x_log [B][ticks+1][12], u_log [B][ticks][12], sqp_iter_log [B][ticks], converged_log
+    [B][ticks], foot_log [B][ticks][2][3], fz_log [B][ticks][2]) device tensors; the last two
+    hold row 0 of each tick's window."""
+    import torch
+    B, N, T = us.shape[0], us.shape[1], int(ticks)
+    dev = xs.device
+    rows = max(T, 0)
+    _check_f64("xs", xs, (B, N + 1, 12), dev)
+    _check_f64("us", us, (B, N, 12), dev)
+    _check_f64("alpha", alpha, (B,), dev)
+    _check_f64("cmd", cmd, (B, rows, 4), dev)
+    _check_gait_state(B, dev, x, ref_pose, foot_now)
+    if wrench is not None:
+        _check_f64("wrench", wrench, (B, rows, 6), dev)
+    gs = gait.struct(B, dev)
+    _check_robots(handle, B)
+    f = dict(dtype=torch.float64, device=dev)
+    x_log = torch.zeros(B, rows + 1, 12, **f)
+    u_log = torch.zeros(B, rows, 12, **f)
+    it_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
+    cv_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
+    foot_log = torch.zeros(B, rows, 2, 3, **f)
+    fz_log = torch.zeros(B, rows, 2, **f)
+    roll = RolloutStruct(T, 0, int(substeps), _tensor_ptr(wrench) or None, float(alpha_reset),
+                         x_log.data_ptr(), u_log.data_ptr() or None, it_log.data_ptr() or None,
+                         cv_log.data_ptr() or None)
+    gio = RolloutGaitStruct(cmd.data_ptr() or None, ref_pose.data_ptr(), foot_now.data_ptr(), int(tick0),
+                            foot_log.data_ptr() or None, fz_log.data_ptr() or None)
+    p = params or default_model_params()
+    lp = ls or default_linesearch()
+    s = settings_struct(settings)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    o = _order_before(handle, 0, True)
+    check(lib().srbd_qp_srbd_rollout_gait_f64(handle.ptr, int(B), C.byref(p), C.byref(gs), C.byref(gio),
+                                              C.byref(lp), C.byref(s), SRBD_CONSTRAINTS[constraints],
+                                              int(sqp_max_loop), C.byref(roll), ptr(xs), ptr(us), ptr(x),
+                                              ptr(alpha)), "srbd_qp_srbd_rollout_gait_f64")
+    _order_after(o)
+    return x_log, u_log, it_log, cv_log, foot_log, fz_log

@@ -284,6 +284,28 @@ struct RolloutRow {
 hipError_t launch_rollout_rows(int batch, const RolloutRow* rows, int nrows, double* alpha,
                                double alpha_value, hipStream_t stream);
 
+// srbd_gait.hip: one tick's plan window from a gait, a command and the measured state
+// (srbd_qp_srbd_gait_plan_f64).  The command carries a stride (doubles per robot), and the
+// optional logs receive row 0 of the feet / fz_max at robot r's log + r * stride, so that the
+// replanning rollout reads column t of its commands and writes column t of its logs from the
+// same launch.
+struct GaitIo {
+  const double* cmd;  // robot r's (vx, vy, wz, height) at cmd + r * cmd_stride
+  long long cmd_stride;
+  const double* x;    // [batch][12] measured state
+  long long tick;
+  double* ref_pose;   // [batch][3] in/out
+  double* foot_now;   // [batch][2][3] in/out
+  double *x_ref, *foot_r, *foot_l, *fz_max;  // the window (dense, the plan's shapes)
+  double* foot_log;   // foot_log + r * foot_log_stride: 6 doubles (NULL: not written)
+  long long foot_log_stride;
+  double* fz_log;     // fz_log + r * fz_log_stride: 2 doubles (NULL: not written)
+  long long fz_log_stride;
+};
+// `robots`: the handle's MODEL role (Lbody[2] of the reference's angular momentum); may be NULL.
+hipError_t launch_srbd_gait(const srbd_model_params& p, int batch, int N, const srbd_gait_f64& gait,
+                            const GaitIo& io, hipStream_t stream, const srbd_robots_f64* robots = nullptr);
+
 // rescue.hip (srbd_qp_settings.f64_rescue / f32_iters): list the QPs with status >=
 // min_status in batch order, widen / narrow QP-major rows of `elems` values between fp32 and fp64
 hipError_t launch_select_unsolved(const int* status, int batch, int min_status, int* idx, int* count,

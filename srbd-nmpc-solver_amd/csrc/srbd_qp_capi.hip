@@ -96,7 +96,7 @@ struct srbd_qp_handle_s {
   // srbd_qp_srbd_nmpc_f64: QP data, solution and loop state
   srbd::Buffer nmpc;
   // srbd_qp_srbd_rollout_f64: the step's sqp_iter / converged (capacity ints each), and the
-  // dense plan window of one tick (first rollout with a plan)
+  // dense plan window of one tick (first rollout with a plan or a gait)
   srbd::Buffer roll, roll_plan;
   // srbd_qp_srbd_set_robots_f64: the two roles' pointers (the caller's arrays; all NULL = clear)
   srbd_robots_f64 robots_model{}, robots_plant{};
@@ -1536,13 +1536,72 @@ int srbd_qp_srbd_advance_f64(srbd_qp_handle h, int batch, const srbd_model_param
   return SRBD_QP_OK;
 }
 
-int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
-                             const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
-                             const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
-                             const srbd_rollout_f64* roll, double* xs, double* us, double* x,
-                             double* alpha) {
+// ---- the gait planner ----
+namespace {
+// the host checks of srbd_qp_srbd_gait_plan_f64 that the replanning rollout shares
+int check_gait(srbd_qp_handle h, int batch, const srbd_gait_f64* g, long long tick) {
+  const srbd_qp_dims& d = h->dims;
+  if (d.nx != 12 || d.nu != 12) return fail(SRBD_QP_EDIM, "the SRBD gait planner needs nx = nu = 12");
+  if (batch < 0 || batch > h->capacity) return fail(SRBD_QP_ECAPACITY, "batch exceeds capacity");
+  if (tick < 0) return fail(SRBD_QP_EINVAL, "gait: tick must be non-negative");
+  if (!g->period_r && g->period < 1) return fail(SRBD_QP_EINVAL, "gait: period must be at least 1");
+  for (int f = 0; f < 2; ++f) {
+    // against the scalar period only where every robot has that period
+    if (!g->swing_r && (g->swing[f] < 0 || (!g->period_r && g->swing[f] >= g->period)))
+      return fail(SRBD_QP_EINVAL, "gait: swing must be in [0, period)");
+    if (!g->offset_r && g->offset[f] < 0) return fail(SRBD_QP_EINVAL, "gait: offset must be non-negative");
+  }
+  if (!(g->fz_swing > 0.0)) return fail(SRBD_QP_EINVAL, "gait: fz_swing must be positive");
+  if (!(g->fz_stance > g->fz_swing)) return fail(SRBD_QP_EINVAL, "gait: fz_stance must exceed fz_swing");
+  return SRBD_QP_OK;
+}
+}  // namespace
+
+int srbd_qp_srbd_gait_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                               const srbd_gait_f64* gait, const double* cmd, const double* x, long long tick,
+                               double* ref_pose, double* foot_now, double* x_ref, double* foot_r,
+                               double* foot_l, double* fz_max, void* stream) {
+  if (!h || !params || !gait || !cmd || !x || !ref_pose || !foot_now || !x_ref || !foot_r || !foot_l || !fz_max)
+    return fail(SRBD_QP_EINVAL, "NULL argument");
+  const int rc = check_gait(h, batch, gait, tick);
+  if (rc) return rc;
+  if (!aligned16(x_ref) || !aligned16(fz_max))
+    return fail(SRBD_QP_EINVAL, "gait: x_ref / fz_max must be 16-byte aligned");
+  if (batch == 0) return SRBD_QP_OK;
+  hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  srbd::DeviceGuard guard(h->device);
+  srbd::GaitIo io{};
+  io.cmd = cmd;
+  io.cmd_stride = 4;
+  io.x = x;
+  io.tick = tick;
+  io.ref_pose = ref_pose;
+  io.foot_now = foot_now;
+  io.x_ref = x_ref;
+  io.foot_r = foot_r;
+  io.foot_l = foot_l;
+  io.fz_max = fz_max;
+  const hipError_t e = srbd::launch_srbd_gait(*params, batch, h->dims.N, *gait, io, strm, &h->robots_model);
+  if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+  return SRBD_QP_OK;
+}
+
+// T ticks of the closed loop: srbd_qp_srbd_rollout_f64 (gait == NULL: the window of tick t is
+// gathered out of `plan`) and srbd_qp_srbd_rollout_gait_f64 (the planner writes it).
+static int rollout_impl(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                        const srbd_plan_f64* plan, const srbd_gait_f64* gait,
+                        const srbd_rollout_gait_f64* gio, const srbd_linesearch_params* ls,
+                        const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                        const srbd_rollout_f64* roll, double* xs, double* us, double* x, double* alpha) {
   if (!h || !params || !ls || !settings || !roll || !xs || !us || !x || !alpha)
     return fail(SRBD_QP_EINVAL, "NULL argument");
+  if (gait) {
+    // (no tick reads a command when there is none)
+    if (!gio || (!gio->cmd && roll->ticks > 0) || !gio->ref_pose || !gio->foot_now)
+      return fail(SRBD_QP_EINVAL, "NULL argument");
+    const int rc = check_gait(h, batch, gait, gio->tick0);
+    if (rc) return rc;
+  }
   const srbd_qp_dims& d = h->dims;
   if (d.nx != 12 || d.nu != 12) return fail(SRBD_QP_EDIM, "the SRBD NMPC loop needs nx = nu = 12");
   if (batch < 0 || batch > h->capacity) return fail(SRBD_QP_ECAPACITY, "batch exceeds capacity");
@@ -1550,8 +1609,8 @@ int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_param
   if (T < 0) return fail(SRBD_QP_EINVAL, "rollout: ticks must be non-negative");
   if (roll->substeps < 1) return fail(SRBD_QP_EINVAL, "rollout: substeps must be at least 1");
   if (!(roll->alpha_reset >= 0.0)) return fail(SRBD_QP_EINVAL, "rollout: alpha_reset must be non-negative");
-  const bool with_plan = plan && (plan->x_ref || plan->foot_r || plan->foot_l || plan->fz_max);
-  if (with_plan && (long long)P < (long long)N + T - 1)
+  const bool with_plan = gait || (plan && (plan->x_ref || plan->foot_r || plan->foot_l || plan->fz_max));
+  if (!gait && with_plan && (long long)P < (long long)N + T - 1)
     return fail(SRBD_QP_EINVAL, "rollout: the plan needs plan_stages >= N + ticks - 1");
   if (!aligned16(xs) || !aligned16(us)) return fail(SRBD_QP_EINVAL, "rollout: xs / us must be 16-byte aligned");
   {  // the step's own checks (settings, constraints against the handle's dims, ...): a step of
@@ -1598,21 +1657,23 @@ int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_param
     double* const wfr = wxr + B * wx;
     double* const wfl = wfr + B * wf;
     double* const wfz = wfl + B * wf;
-    if (plan->x_ref) {
+    if (gait) win = srbd_plan_f64{wxr, wfr, wfl, wfz};  // the planner writes all four
+    const srbd_plan_f64 src = gait ? srbd_plan_f64{} : *plan;  // what is gathered
+    if (src.x_ref) {
       win.x_ref = wxr;
-      rows[nrows++] = srbd::RolloutRow{plan->x_ref, wxr, (int)wx, 12 * ((long long)P + 1), (long long)wx};
+      rows[nrows++] = srbd::RolloutRow{src.x_ref, wxr, (int)wx, 12 * ((long long)P + 1), (long long)wx};
     }
-    if (plan->foot_r) {
+    if (src.foot_r) {
       win.foot_r = wfr;
-      rows[nrows++] = srbd::RolloutRow{plan->foot_r, wfr, (int)wf, 3 * (long long)P, (long long)wf};
+      rows[nrows++] = srbd::RolloutRow{src.foot_r, wfr, (int)wf, 3 * (long long)P, (long long)wf};
     }
-    if (plan->foot_l) {
+    if (src.foot_l) {
       win.foot_l = wfl;
-      rows[nrows++] = srbd::RolloutRow{plan->foot_l, wfl, (int)wf, 3 * (long long)P, (long long)wf};
+      rows[nrows++] = srbd::RolloutRow{src.foot_l, wfl, (int)wf, 3 * (long long)P, (long long)wf};
     }
-    if (plan->fz_max) {
+    if (src.fz_max) {
       win.fz_max = wfz;
-      rows[nrows++] = srbd::RolloutRow{plan->fz_max, wfz, (int)wz, 2 * (long long)P, (long long)wz};
+      rows[nrows++] = srbd::RolloutRow{src.fz_max, wfz, (int)wz, 2 * (long long)P, (long long)wz};
     }
   }
   const int per_stage[4] = {12, 3, 3, 2};  // doubles per stage of x_ref, foot_r, foot_l, fz_max
@@ -1620,7 +1681,25 @@ int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_param
     // W_t: stages t .. t + N of the long plan, gathered dense; alpha per the reset policy
     srbd::RolloutRow rt[4];
     int n = 0;
-    if (with_plan) {
+    if (gait) {  // W_t from the planner: cmd[:, t], the current x, tick0 + t; row 0 to the logs
+      srbd::GaitIo gi{};
+      gi.cmd = gio->cmd + (size_t)t * 4;
+      gi.cmd_stride = (long long)T * 4;
+      gi.x = x;
+      gi.tick = gio->tick0 + t;
+      gi.ref_pose = gio->ref_pose;
+      gi.foot_now = gio->foot_now;
+      gi.x_ref = const_cast<double*>(win.x_ref);
+      gi.foot_r = const_cast<double*>(win.foot_r);
+      gi.foot_l = const_cast<double*>(win.foot_l);
+      gi.fz_max = const_cast<double*>(win.fz_max);
+      gi.foot_log = gio->foot_log ? gio->foot_log + (size_t)t * 6 : nullptr;
+      gi.foot_log_stride = (long long)T * 6;
+      gi.fz_log = gio->fz_log ? gio->fz_log + (size_t)t * 2 : nullptr;
+      gi.fz_log_stride = (long long)T * 2;
+      e = srbd::launch_srbd_gait(*params, batch, N, *gait, gi, strm, &h->robots_model);
+      if (e != hipSuccess) return device_error(e, "rollout: ");
+    } else if (with_plan) {
       const double* fields[4] = {plan->x_ref, plan->foot_r, plan->foot_l, plan->fz_max};
       for (int fi = 0; fi < 4; ++fi)
         if (fields[fi]) {
@@ -1658,6 +1737,24 @@ int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_param
   e = hipStreamSynchronize(strm);
   if (e != hipSuccess) return device_error(e, "rollout: ");
   return SRBD_QP_OK;
+}
+
+int srbd_qp_srbd_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                             const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                             const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                             const srbd_rollout_f64* roll, double* xs, double* us, double* x,
+                             double* alpha) {
+  return rollout_impl(h, batch, params, plan, nullptr, nullptr, ls, settings, constraints, sqp_max_loop, roll,
+                      xs, us, x, alpha);
+}
+int srbd_qp_srbd_rollout_gait_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                  const srbd_gait_f64* gait, const srbd_rollout_gait_f64* gio,
+                                  const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
+                                  int constraints, int sqp_max_loop, const srbd_rollout_f64* roll,
+                                  double* xs, double* us, double* x, double* alpha) {
+  if (!gait || !gio) return fail(SRBD_QP_EINVAL, "NULL argument");
+  return rollout_impl(h, batch, params, nullptr, gait, gio, ls, settings, constraints, sqp_max_loop, roll, xs,
+                      us, x, alpha);
 }
 
 int srbd_qp_solve_f32(srbd_qp_handle h, int batch, const srbd_qp_settings* st,

@@ -30,7 +30,7 @@ import numpy as np
 from .qp import OcpQpBatch
 
 __all__ = ["SrbdParams", "SrbdPlan", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier",
-           "plant_step", "shift_guess"]
+           "plant_step", "shift_guess", "SrbdGait", "gait_plan"]
 
 
 @dataclass(frozen=True)
@@ -291,6 +291,92 @@ def shift_guess(xs, us, p: SrbdParams, plan: Optional[SrbdPlan] = None):
     xs_new = np.concatenate([xs[:, 1:], xN[:, None]], axis=1)
     us_new = np.concatenate([us[:, 1:], us[:, N - 1:]], axis=1)
     return xs_new, us_new
+
+
+# ---------------------------------------------------------------------------
+# the gait planner (the C-ABI's srbd_qp_srbd_gait_plan_f64)
+# ---------------------------------------------------------------------------
+@dataclass(frozen=True)
+class SrbdGait:
+    """The C-ABI's srbd_gait_f64.  period, swing, offset are in stages: an int / a pair
+    (right, left) for every robot, or arrays [B] / [B][2] (the struct's _r arrays)."""
+    period: object = 1
+    swing: object = (0, 0)
+    offset: object = (0, 0)
+    hip: Tuple[Tuple[float, float], Tuple[float, float]] = ((0.0, -0.1), (0.0, 0.1))
+    ground_z: float = 0.0
+    k_raibert: float = 0.0
+    fz_stance: float = 1000.0
+    fz_swing: float = 1.0
+    anchor: int = 0
+
+
+def gait_plan(p: SrbdParams, gait: SrbdGait, cmd, x, tick: int, ref_pose, foot_now, N: Optional[int] = None,
+              Lbody_z=None):
+    """One tick's plan window, the statement of include/srbd_qp.h's gait planner: cmd [B][4]
+    (vx, vy in the heading frame, wz, body height), x [B][12] the measured state, tick >= 0,
+    ref_pose [B][3] (px, py, yaw), foot_now [B][2][3].  N: the horizon (None: p.N); Lbody_z [B]:
+    the robots' Lbody[2] (None: p.Lbody[2]).  Returns (SrbdPlan, new ref_pose, new foot_now);
+    the inputs are left alone."""
+    cmd, x = np.asarray(cmd, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    ref_pose, foot_now = np.asarray(ref_pose, dtype=np.float64), np.asarray(foot_now, dtype=np.float64)
+    B = cmd.shape[0]
+    N = p.N if N is None else int(N)
+    if tick < 0:
+        raise ValueError("tick must be non-negative")
+    if not gait.fz_swing > 0.0 or not gait.fz_stance > gait.fz_swing:
+        raise ValueError("fz_swing must be positive and fz_stance above it")
+    period = np.broadcast_to(np.asarray(gait.period, dtype=np.int64), (B,))
+    swing = np.broadcast_to(np.asarray(gait.swing, dtype=np.int64), (B, 2))
+    offset = np.broadcast_to(np.asarray(gait.offset, dtype=np.int64), (B, 2))
+    dt = p.dt
+    vx, vy, wz, zh = (cmd[:, i, None] for i in range(4))  # [B][1]
+    c, vm = x[:, 6:8], x[:, 9:11]
+    k = np.arange(N + 1)
+    # reference
+    yaw = ref_pose[:, 2, None] + k * (dt * wz)  # [B][N+1]
+    cs, sn = np.cos(yaw), np.sin(yaw)
+    vw = np.stack([cs * vx - sn * vy, sn * vx + cs * vy], axis=-1)  # Rz(yaw_k)(vx, vy)
+    p0 = c if gait.anchor else ref_pose[:, 0:2]
+    pk = np.empty((B, N + 1, 2))
+    pk[:, 0] = p0
+    for i in range(N):
+        pk[:, i + 1] = pk[:, i] + dt * vw[:, i]
+    Lz = p.Lbody[2] if Lbody_z is None else np.asarray(Lbody_z, dtype=np.float64)[:, None]
+    x_ref = np.zeros((B, N + 1, 12))
+    x_ref[:, :, 2] = yaw
+    x_ref[:, :, 5] = Lz * wz
+    x_ref[:, :, 6:8] = pk
+    x_ref[:, :, 8] = zh
+    x_ref[:, :, 9:11] = vw
+    # contact schedule and feet
+    ks = k[:N]
+    fz = np.empty((B, N, 2))
+    feet = []
+    fb = gait.k_raibert * (vm - vw[:, 0])  # [B][2]
+    for f in range(2):
+        sw = swing[:, f, None]
+        phi = (int(tick) + ks + offset[:, f, None]) % period[:, None]  # [B][N], int64
+        swinging = phi < sw
+        fz[:, :, f] = np.where(swinging, gait.fz_swing, gait.fz_stance)
+        s = ks - (phi - sw)  # a stance stage: the first stage of that stance
+        down = ~swinging & ((sw == 0) | (s <= 0))
+        j = np.where(swinging, ks + sw - phi, s)
+        jc = np.clip(j, 0, N)  # j' = min(j, N); j < 0 only where the foot is down
+        half = (period - swing[:, f])[:, None] * dt / 2.0
+        hx = gait.hip[f][0] + half * vx  # [B][1]
+        hy = gait.hip[f][1] + half * vy
+        cj, sj = np.take_along_axis(cs, jc, 1), np.take_along_axis(sn, jc, 1)
+        pj = np.take_along_axis(pk, jc[:, :, None], 1)  # [B][N][2]
+        F = np.empty((B, N, 3))
+        F[:, :, 0] = c[:, None, 0] + (pj[:, :, 0] - p0[:, None, 0]) + (cj * hx - sj * hy) + fb[:, None, 0]
+        F[:, :, 1] = c[:, None, 1] + (pj[:, :, 1] - p0[:, None, 1]) + (sj * hx + cj * hy) + fb[:, None, 1]
+        F[:, :, 2] = gait.ground_z
+        feet.append(np.where(down[:, :, None], foot_now[:, f, None, :], F))
+    plan = SrbdPlan(x_ref=x_ref, foot_r=feet[0], foot_l=feet[1], fz_max=fz)
+    new_pose = np.concatenate([pk[:, 1], yaw[:, 1:2]], axis=1)
+    new_feet = np.stack([feet[0][:, 0], feet[1][:, 0]], axis=1)
+    return plan, new_pose, new_feet
 
 
 def friction_cone(p: SrbdParams):
