@@ -37,6 +37,9 @@
  *   srbd_qp_srbd_gait_plan_f64   the producer of a tick's plan: a velocity command, a gait and
  *                                the measured state in, the window out (Raibert footholds).
  *   srbd_qp_srbd_rollout_gait_f64  the rollout that replans every tick.
+ *   srbd_qp_srbd_set_terrain_f64 height maps under the gait planner: foothold height, reference
+ *                                body height and foothold selection; srbd_qp_srbd_terrain_height_f64
+ *                                samples them.
  *
  * ------------------------------------------------------------------------
  * Problem (per QP, stages k = 0..N), identical to hpipm::OcpQp
@@ -649,8 +652,8 @@ int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f6
  * NULL, period < 1, swing[f] outside [0, period) or offset[f] < 0 are SRBD_QP_EINVAL; so are
  * fz_swing <= 0 and fz_stance <= fz_swing; the handle needs nx = nu = 12 (SRBD_QP_EDIM);
  * batch above the capacity is SRBD_QP_ECAPACITY; batch == 0 returns SRBD_QP_OK.
- * Not per robot (out of scope): hip, the gains, fz_stance / fz_swing; terrain height and
- * swing-foot trajectories (the model has no foot states).
+ * Not per robot (out of scope): hip, the gains, fz_stance / fz_swing; swing-foot trajectories
+ * (the model has no foot states).  Terrain height under a foothold: srbd_qp_srbd_set_terrain_f64.
  * ---------------------------------------------------------------------- */
 typedef struct srbd_gait_f64 {
   int period, swing[2], offset[2];  /* in stages; every robot's where the arrays below are NULL */
@@ -695,6 +698,58 @@ int srbd_qp_srbd_rollout_gait_f64(srbd_qp_handle h, int batch, const srbd_model_
                                   const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
                                   int constraints, int sqp_max_loop, const srbd_rollout_f64* roll,
                                   double* xs, double* us, double* x, double* alpha);
+
+/* ------------------------------------------------------------------------
+ * Terrain (additive to ABI 12): a shared set of height maps under the gait planner, with a
+ * per-robot map index, so that one batch walks slopes, stairs and rough ground.  It attaches
+ * to the handle; srbd_qp_srbd_gait_plan_f64 and srbd_qp_srbd_rollout_gait_f64 issued afterwards
+ * on that handle read it.  The call copies the struct and does no device work; the arrays are
+ * device memory read by the launched kernels: keep them alive and unchanged until those have
+ * finished.  terrain == NULL, or a NULL height, clears it; with the terrain cleared the
+ * planner is what it is without this entry point: the same kernel code, the same bits.
+ * Height of map m at (x, y), clamped bilinear, H = height + m ny nx:
+ *   s = (x - x0) / cell, clamped to [0, nx - 1];  i = min(floor(s), nx - 2),  a = s - i;
+ *   t = (y - y0) / cell, clamped to [0, ny - 1];  j = min(floor(t), ny - 2),  b = t - j;
+ *   h = (1 - b)((1 - a) H[j][i] + a H[j][i+1]) + b ((1 - a) H[j+1][i] + a H[j+1][i+1]).
+ *   Outside the grid the edge value extends.
+ * The planner with a terrain set, robot r on map m = map_r[r] (everything not named here is
+ * the gait planner's definition above):
+ *   Reference height: x_ref[k][8] = zh + h(p_k), k = 0..N; the other entries are unchanged.
+ *   Foothold of a touchdown: n = the planner's F_f(j).xy, the nominal foothold.  Candidates
+ *     d = (di, dj), |di|, |dj| <= search, with index q = (dj + search)(2 search + 1) + (di + search)
+ *     and position c_d = n + cell (di, dj).  Roughness rho(c) = the largest of
+ *     |h(c +- cell e_x) - h(c)| and |h(c +- cell e_y) - h(c)|;  cost
+ *     J_d = cell^2 (di^2 + dj^2) + w_rough rho(c_d)^2.  The chosen d* has the smallest J, ties
+ *     go to the smallest q.  F_f(j).xy = c_d*,  F_f(j).z = ground_z + h(c_d*).  With search == 0
+ *     no roughness is evaluated and F.xy has the bits of n.
+ *   Rows and state: which rows hold foot_now and which hold F_f of which touchdown stays as it
+ *     is, and so do the latch and ref_pose: a foot in stance keeps the height it landed on, bit
+ *     for bit; a swinging foot's target, z included, is recomputed every tick.
+ * Caller's contract (device data, not checked): map_r's values in [0, maps), finite heights.
+ * Checks: NULL handle, maps < 1, nx or ny < 2, cell not > 0, search outside 0..3, w_rough < 0
+ * or not finite, x0 or y0 not finite are SRBD_QP_EINVAL; a handle without nx = nu = 12 is
+ * SRBD_QP_EDIM.
+ * Out of scope: a plant that knows the ground (it applies u0 at the planned foot, wherever
+ * that is), swing clearance and swing trajectories, a vertical-velocity or tilt reference on
+ * slopes, one private map per robot (the map index covers it), srbd_qp_multi_*, the
+ * hpipm-cpp shim, fp32.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_terrain_f64 {
+  const double* height;  /* device, [maps][ny][nx]; sample (j, i) lies at (x0 + i cell, y0 + j cell) */
+  int maps, nx, ny;      /* maps >= 1; nx, ny >= 2 */
+  double x0, y0, cell;   /* cell > 0 */
+  const int* map_r;      /* device [batch], optional: robot i's map in [0, maps); NULL = map 0 */
+  int search;            /* 0..3: foothold candidates within +-search cells of the nominal one */
+  double w_rough;        /* >= 0: weight of the local roughness in the candidate's cost */
+} srbd_terrain_f64;
+int srbd_qp_srbd_set_terrain_f64(srbd_qp_handle h, const srbd_terrain_f64* terrain);
+
+/* The public sampler: out[i] = the height of map[i] (NULL: map 0) at xy[i], the formula above.
+ * Asynchronous on `stream` (NULL = the handle's own); xy, map, out are device memory.  Caller's
+ * contract: map's values in [0, maps), finite coordinates.  Checks: a NULL handle, no terrain
+ * set, n < 0 and, for n > 0, a NULL xy or out are SRBD_QP_EINVAL; n == 0 returns SRBD_QP_OK. */
+int srbd_qp_srbd_terrain_height_f64(srbd_qp_handle h, int n, const double* xy /*[n][2]*/,
+                                    const int* map /*[n], NULL = 0*/, double* out /*[n]*/, void* stream);
 
 /* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,

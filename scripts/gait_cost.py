@@ -9,9 +9,16 @@
     windows are that constant plan bit for bit, so both run the same SQP iterations: BOX_U,
     each robot from the reference's cold start, alternating, the smallest of --runs each.
 
+With --terrain the planner alone is measured again with a terrain on the
+handle, for search 0, 1 and 3, on one 256 x 256 map of random heights and on 16 such maps with
+a random map per robot ("planner_terrain_us": median and smallest per case).  --planner-only
+skips the ticks.  The planner without terrain also runs on a library built from an older commit
+(SRBD_QP_LIB=...), for A/B runs.
+
 Prints one JSON line.  A measurement, not a pass / fail line.
 
 Usage: python scripts/gait_cost.py [--batch 65536] [--N 20] [--ticks 3] [--runs 2] [--repeats 50]
+                                   [--terrain] [--planner-only]
 """
 import argparse
 import json
@@ -35,6 +42,8 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--terrain", action="store_true")
+    ap.add_argument("--planner-only", action="store_true")
     args = ap.parse_args()
     import torch
     pkg = bench.import_pkg()
@@ -59,17 +68,43 @@ def main():
     ext = h.torch_stream()
     win = capi.srbd_gait_plan(h, walk, cmd, x, 0, pose, feet)
     torch.cuda.synchronize()
-    times = []
-    with torch.cuda.stream(ext):
-        for r in range(5 + args.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            capi.srbd_gait_plan(h, walk, cmd, x, r + 1, pose, feet, stream=h.stream(), out=win)
-            e1.record()
-            times.append((e0, e1))
-    torch.cuda.synchronize()
-    us = [a.elapsed_time(b) * 1e3 for a, b in times[5:]]
+
+    def planner_us():
+        times = []
+        with torch.cuda.stream(ext):
+            for r in range(5 + args.repeats):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                capi.srbd_gait_plan(h, walk, cmd, x, r + 1, pose, feet, stream=h.stream(), out=win)
+                e1.record()
+                times.append((e0, e1))
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) * 1e3 for a, b in times[5:]]
+
+    us = planner_us()
     window_bytes = (12 * (N + 1) + 8 * N) * 8 * batch
+    out = {"script": "gait_cost", "batch": batch, "N": N, "ticks": T,
+           "planner_us_median": round(statistics.median(us), 1), "planner_us_min": round(min(us), 1),
+           "window_MB": round(window_bytes / 1e6, 1),
+           "planner_TBps_at_median": round(window_bytes / statistics.median(us) / 1e6, 2)}
+    if args.terrain:  # 5 cm cells around the robots: the footholds fall inside the maps
+        out["planner_terrain_us"] = {}
+        for maps in (1, 16):
+            height = torch.from_numpy(rng.uniform(0.0, 0.05, size=(maps, 256, 256))).to(device)
+            map_r = torch.from_numpy(rng.integers(0, maps, size=batch).astype(np.int32)).to(device)
+            for search in (0, 1, 3):
+                h.set_terrain(capi.Terrain(height, xr[6] - 6.4, xr[7] - 6.4, 0.05, map_r=map_r if maps > 1 else None,
+                                           search=search, w_rough=10.0))
+                t = planner_us()
+                out["planner_terrain_us"][f"maps{maps}_search{search}"] = [round(statistics.median(t), 1),
+                                                                           round(min(t), 1)]
+        h.set_terrain(None)
+        t = planner_us()  # cleared again: the planner without terrain
+        out["planner_cleared_us"] = [round(statistics.median(t), 1), round(min(t), 1)]
+    if args.planner_only:
+        print(json.dumps(out))
+        h.close()
+        return
 
     # ---- the tick, with a constant plan and replanned ----
     _, _, dx0 = pkg.srbd_model.sample_trajectories(batch, N, args.seed + 7, p)
@@ -109,14 +144,10 @@ def main():
             ms[gait].append(round(t, 2))
             ms[("logs", gait)] = logs
     same = all(torch.equal(a, b) for a, b in zip(ms[("logs", False)], ms[("logs", True)][:4]))
-    out = {"script": "gait_cost", "batch": batch, "N": N, "ticks": T,
-           "planner_us_median": round(statistics.median(us), 1), "planner_us_min": round(min(us), 1),
-           "window_MB": round(window_bytes / 1e6, 1),
-           "planner_TBps_at_median": round(window_bytes / statistics.median(us) / 1e6, 2),
-           "rollout_plan_ms": ms[False], "rollout_gait_ms": ms[True],
+    out.update({"rollout_plan_ms": ms[False], "rollout_gait_ms": ms[True],
            "ms_per_tick_plan_min": round(min(ms[False]) / T, 2), "ms_per_tick_gait_min": round(min(ms[True]) / T, 2),
            "sqp_iters_mean_per_tick": [round(float(v), 3) for v in ms[("logs", True)][2].float().mean(dim=0)],
-           "gait_rollout_equals_plan_rollout": bool(same)}
+           "gait_rollout_equals_plan_rollout": bool(same)})
     print(json.dumps(out))
     h.close()
 

@@ -25,6 +25,14 @@ of gait_host.walking_case through gait_host.closed_loop, which plans every tick 
 measured state, so the perturbation of x reaches the later windows through the feedback.
 
     python scripts/rollout_sensitivity.py --gait --seed 30
+
+With --gait --terrain the same for tests/test_gpu_terrain.py's rollout up the stairs (DESIGN.md
+4.7f): terrain_host.stairs_case through terrain_host.closed_loop (search 1), with two more
+conditions on the inputs: the smallest gap between the best and the second-best foothold cost
+over every touchdown of every tick (wanted >= 1e-6 cell^2), and the chosen candidates, which like
+the iteration counts must not change under the perturbation; the feet's d_t is printed too.
+
+    python scripts/rollout_sensitivity.py --gait --terrain --seed 30
 """
 import argparse
 import sys
@@ -40,6 +48,7 @@ import gait_host as GH  # noqa: E402
 import helpers  # noqa: E402
 import robots_host as BH  # noqa: E402
 import rollout_host as RH  # noqa: E402
+import terrain_host as TH  # noqa: E402
 
 NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
             tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
@@ -50,11 +59,15 @@ B, N, T = 4, 10, 4
 
 ROBOTS = None  # --robots: (model list, plant list)
 GAIT = False   # --gait: the inputs are gait_host.walking_case's
+TERRAIN = None  # --gait --terrain: the SrbdTerrain; the inputs are terrain_host.stairs_case's
 
 
 def run(sm, oracle, p, case, inputs):
     if GAIT:
         xs, us, x, alpha, gait, cmd, ref_pose, foot_now = inputs
+        if TERRAIN is not None:
+            return TH.closed_loop(sm, oracle, p, gait, TERRAIN, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC,
+                                  15, case[0], alpha_reset=case[1])
         return GH.closed_loop(sm, oracle, p, gait, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, 15,
                               case[0], alpha_reset=case[1])
     xs, us, x, alpha, plan = inputs
@@ -65,7 +78,10 @@ def run(sm, oracle, p, case, inputs):
 
 
 def conditions(sm, oracle, p, seed):
-    inputs = (GH if GAIT else RH).walking_case(sm, p, B, N, T, seed)
+    if TERRAIN is not None:
+        inputs = TH.stairs_case(sm, p, B, N, T, seed)
+    else:
+        inputs = (GH if GAIT else RH).walking_case(sm, p, B, N, T, seed)
     out = {}
     for case in CASES:
         h = run(sm, oracle, p, case, inputs)
@@ -74,19 +90,29 @@ def conditions(sm, oracle, p, seed):
 
 
 def main():
-    global ROBOTS, GAIT
+    global ROBOTS, GAIT, TERRAIN
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=30)
     ap.add_argument("--search", type=int, nargs=2, metavar=("FROM", "TO"))
     ap.add_argument("--draws", type=int, default=3)
     ap.add_argument("--robots", action="store_true")
     ap.add_argument("--gait", action="store_true")
+    ap.add_argument("--terrain", action="store_true")
     a = ap.parse_args()
+    if a.terrain and not a.gait:
+        ap.error("--terrain goes with --gait")
     if a.gait and a.robots:
         ap.error("--gait and --robots are separate tables")
     GAIT = a.gait
     sm, oracle = helpers.load_package().srbd_model, helpers.load_oracle()
     p = sm.SrbdParams()
+    if a.terrain:
+        TERRAIN = TH.stairs_terrain(sm)
+        global CASES
+        CASES = [(c, 0.0) for c in ("none", "box_u")]  # the terrain test's cases
+
+    def sel(h):  # the selection margin in cell^2
+        return h["select_margin"] / TERRAIN.cell ** 2
 
     def set_robots(seed):
         global ROBOTS
@@ -98,7 +124,12 @@ def main():
             set_robots(seed)
             _, c = conditions(sm, oracle, p, seed)
             ok = all(m >= 1e-6 and len(its) >= 2 for m, its, _ in c.values())
-            print(seed, "OK " if ok else "-- ", {k: (f"{m:.1e}", its) for k, (m, its, _) in c.items()}, flush=True)
+            extra = ""
+            if a.terrain:
+                ok = ok and all(sel(h) >= 1e-6 for _, _, h in c.values())
+                extra = {k: f"select {sel(h):.1e}" for k, (_, _, h) in c.items()}
+            print(seed, "OK " if ok else "-- ", {k: (f"{m:.1e}", its) for k, (m, its, _) in c.items()}, extra,
+                  flush=True)
         return
     set_robots(a.seed)
     inputs, c = conditions(sm, oracle, p, a.seed)
@@ -106,7 +137,9 @@ def main():
     for case in CASES:
         margin, its, base = c[case]
         print(f"{case}: margin {margin:.2e}, sqp iterations {its}\n{base['sqp_iter']}")
-        dx, du = np.zeros(T), np.zeros(T)
+        dx, du, df = np.zeros(T), np.zeros(T), np.zeros(T)
+        if a.terrain:
+            print(f"  selection margin {sel(base):.2e} cell^2, chosen candidates of row 0\n{base['q_log']}")
         for d in range(a.draws):
             rng = np.random.default_rng([a.seed, d])
             pert = lambda v: v * (1.0 + 1e-7 * rng.choice([-1.0, 1.0], size=v.shape))
@@ -115,8 +148,11 @@ def main():
             dx = np.maximum(dx, np.abs(h["x_log"][:, 1:] - base["x_log"][:, 1:]).max(axis=(0, 2)))
             du = np.maximum(du, np.abs(h["u_log"] - base["u_log"]).max(axis=(0, 2)))
             print(f"  draw {d}: same iteration counts {same}")
+            if a.terrain:
+                df = np.maximum(df, np.abs(h["foot_log"] - base["foot_log"]).max(axis=(0, 2, 3)))
+                print(f"  draw {d}: same chosen candidates {np.array_equal(h['q_log'], base['q_log'])}")
         fmt = lambda v: "(" + ", ".join(f"{e:.1e}" for e in v) + ")"
-        print(f"    {case!r}: ({fmt(dx)}, {fmt(du)}),")
+        print(f"    {case!r}: ({fmt(dx)}, {fmt(du)}" + (f", {fmt(df)}" if a.terrain else "") + "),")
         if ROBOTS:
             both = ROBOTS
             ROBOTS = (both[0], both[0])

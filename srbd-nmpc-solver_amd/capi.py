@@ -210,6 +210,58 @@ class Robots:
         return rs
 
 
+class TerrainStruct(C.Structure):
+    """srbd_terrain_f64."""
+    _fields_ = [("height", _dp), ("maps", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("x0", C.c_double),
+                ("y0", C.c_double), ("cell", C.c_double), ("map_r", _dp), ("search", C.c_int),
+                ("w_rough", C.c_double)]
+
+
+class Terrain:
+    """Height maps for Handle.set_terrain (srbd_terrain_f64).  height: a torch fp64 device tensor
+    [maps][ny][nx], or [ny][nx] for one map; sample (j, i) lies at (x0 + i cell, y0 + j cell) and
+    the height between samples is the clamped bilinear of include/srbd_qp.h.  map_r: an int32
+    device tensor [B], robot i's map (None: map 0; its values are the caller's contract).
+    search (0..3): the planner picks each touchdown among the (2 search + 1)^2 cells around the
+    nominal foothold, by cell^2 |d|^2 + w_rough roughness^2.  Dtype, contiguity, shapes and
+    device are checked here, with ValueError; the numbers by the library."""
+
+    def __init__(self, height, x0, y0, cell, map_r=None, search=0, w_rough=0.0):
+        self.height, self.x0, self.y0, self.cell = height, x0, y0, cell
+        self.map_r, self.search, self.w_rough = map_r, search, w_rough
+        self.rows = None
+
+    def struct(self, device=None) -> TerrainStruct:
+        import torch
+        h = self.height
+        if not isinstance(h, torch.Tensor) or h.dtype != torch.float64:
+            raise ValueError("terrain.height must be a torch.float64 tensor")
+        if h.dim() not in (2, 3):
+            raise ValueError(f"terrain.height has shape {tuple(h.shape)}, expected [maps][ny][nx] or [ny][nx]")
+        if not h.is_contiguous():
+            raise ValueError("terrain.height must be contiguous")
+        if h.device.type != "cuda" or (device is not None and h.device != device):
+            raise ValueError(f"terrain.height is on {h.device}, the handle on "
+                             f"{device if device is not None else 'a GPU'}")
+        maps = h.shape[0] if h.dim() == 3 else 1
+        ts = TerrainStruct(h.data_ptr() or None, int(maps), int(h.shape[-1]), int(h.shape[-2]), float(self.x0),
+                           float(self.y0), float(self.cell), None, int(self.search), float(self.w_rough))
+        m = self.map_r
+        self.rows = None
+        if m is not None:
+            if not isinstance(m, torch.Tensor) or m.dtype != torch.int32:
+                raise ValueError("terrain.map_r must be a torch.int32 tensor")
+            if m.dim() != 1 or m.shape[0] < 1:
+                raise ValueError(f"terrain.map_r has shape {tuple(m.shape)}, expected (B,)")
+            if not m.is_contiguous():
+                raise ValueError("terrain.map_r must be contiguous")
+            if m.device != h.device:
+                raise ValueError(f"terrain.map_r is on {m.device}, the height on {h.device}")
+            ts.map_r = m.data_ptr()
+            self.rows = int(m.shape[0])
+        return ts
+
+
 class AdvanceStruct(C.Structure):
     """srbd_advance_f64."""
     _fields_ = [("substeps", C.c_int), ("wrench", _dp)]
@@ -414,6 +466,11 @@ def lib():
         if hasattr(L, "srbd_qp_srbd_set_robots_f64"):  # robots (older builds: A/B runs)
             L.srbd_qp_srbd_set_robots_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(RobotsStruct)]
             L.srbd_qp_srbd_set_robots_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_srbd_set_terrain_f64"):  # terrain (older builds: A/B runs)
+            L.srbd_qp_srbd_set_terrain_f64.argtypes = [C.c_void_p, C.POINTER(TerrainStruct)]
+            L.srbd_qp_srbd_set_terrain_f64.restype = C.c_int
+            L.srbd_qp_srbd_terrain_height_f64.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+            L.srbd_qp_srbd_terrain_height_f64.restype = C.c_int
         if hasattr(L, "srbd_qp_srbd_gait_plan_f64"):  # the gait planner (older builds: A/B runs)
             L.srbd_qp_srbd_gait_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
                                                      C.POINTER(GaitStruct), C.c_void_p, C.c_void_p,
@@ -562,6 +619,18 @@ class Handle:
                                                     None if rs is None else C.byref(rs)),
                   "srbd_qp_srbd_set_robots_f64")
         self._robots = (model, plant)
+
+    def set_terrain(self, terrain: Optional["Terrain"] = None) -> None:
+        """srbd_qp_srbd_set_terrain_f64: srbd_gait_plan and srbd_rollout_gait on this handle
+        afterwards sample foothold height and reference body height from the Terrain's maps and
+        select footholds on them.  None clears it: the planner without terrain, bit for bit.  The
+        handle keeps the Terrain, and so its tensors, alive until it is replaced; do not modify
+        them while launches that read them are in flight."""
+        import torch
+        ts = None if terrain is None else terrain.struct(torch.device("cuda", self.device))
+        check(lib().srbd_qp_srbd_set_terrain_f64(self._h, None if ts is None else C.byref(ts)),
+              "srbd_qp_srbd_set_terrain_f64")
+        self._terrain = terrain
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -741,6 +810,13 @@ def _check_robots(handle, B) -> None:
     for r in getattr(handle, "_robots", ()):
         if r is not None and r.rows is not None and r.rows < int(B):
             raise ValueError(f"the handle's robots have {r.rows} rows, the batch {int(B)}")
+
+
+def _check_terrain(handle, B) -> None:
+    """The handle's terrain (Handle.set_terrain) reads map_r at rows 0..B-1: ValueError if it has fewer."""
+    t = getattr(handle, "_terrain", None)
+    if t is not None and t.rows is not None and t.rows < int(B):
+        raise ValueError(f"the handle's terrain has a map_r of {t.rows} rows, the batch {int(B)}")
 
 
 def _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream):
@@ -987,6 +1063,7 @@ def srbd_gait_plan(handle: Handle, gait: Gait, cmd, x, tick: int, ref_pose, foot
         raise ValueError("out needs all four of x_ref, foot_r, foot_l, fz_max")
     out.struct(B, N, dev)  # the shapes
     _check_robots(handle, B)
+    _check_terrain(handle, B)
     p = params or default_model_params()
     ptr = lambda t: C.c_void_p(t.data_ptr())
     o = _order_before(handle, stream, True)
@@ -1022,6 +1099,7 @@ def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pos
         _check_f64("wrench", wrench, (B, rows, 6), dev)
     gs = gait.struct(B, dev)
     _check_robots(handle, B)
+    _check_terrain(handle, B)
     f = dict(dtype=torch.float64, device=dev)
     x_log = torch.zeros(B, rows + 1, 12, **f)
     u_log = torch.zeros(B, rows, 12, **f)
@@ -1045,3 +1123,27 @@ def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pos
                                               ptr(alpha)), "srbd_qp_srbd_rollout_gait_f64")
     _order_after(o)
     return x_log, u_log, it_log, cv_log, foot_log, fz_log
+
+
+def srbd_terrain_height(handle: Handle, xy, map=None, stream: int = 0):
+    """The height of the handle's terrain (Handle.set_terrain) at the points xy [n][2], point i
+    on map[i] (an int32 device tensor [n]; None: map 0): srbd_qp_srbd_terrain_height_f64, the
+    clamped bilinear the planner samples.  Torch fp64 device tensors; asynchronous on the
+    handle's stream, ordered like a torch op.  Returns out [n]."""
+    import torch
+    if not isinstance(xy, torch.Tensor) or xy.dim() != 2:
+        raise ValueError("xy must be a torch.float64 tensor [n][2]")
+    n, dev = xy.shape[0], xy.device
+    _check_f64("xy", xy, (n, 2), dev)
+    if map is not None:
+        if not isinstance(map, torch.Tensor) or map.dtype != torch.int32 or tuple(map.shape) != (n,) \
+                or not map.is_contiguous() or map.device != dev:
+            raise ValueError(f"map must be a contiguous torch.int32 tensor of shape ({n},) on {dev}")
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    o = _order_before(handle, stream, True)
+    check(lib().srbd_qp_srbd_terrain_height_f64(handle.ptr, int(n), C.c_void_p(xy.data_ptr() or None),
+                                                C.c_void_p(_tensor_ptr(map) or None),
+                                                C.c_void_p(out.data_ptr() or None), C.c_void_p(stream or None)),
+          "srbd_qp_srbd_terrain_height_f64")
+    _order_after(o)
+    return out

@@ -303,8 +303,14 @@ struct GaitIo {
   long long fz_log_stride;
 };
 // `robots`: the handle's MODEL role (Lbody[2] of the reference's angular momentum); may be NULL.
+// `terrain`: the handle's height maps (srbd_qp_srbd_set_terrain_f64); NULL or a NULL height is
+// the planner without terrain, the other instantiation of the kernel.
 hipError_t launch_srbd_gait(const srbd_model_params& p, int batch, int N, const srbd_gait_f64& gait,
-                            const GaitIo& io, hipStream_t stream, const srbd_robots_f64* robots = nullptr);
+                            const GaitIo& io, hipStream_t stream, const srbd_robots_f64* robots = nullptr,
+                            const srbd_terrain_f64* terrain = nullptr);
+// srbd_qp_srbd_terrain_height_f64: out[i] = the height of map[i] (NULL: map 0) at xy[i]
+hipError_t launch_srbd_terrain_height(const srbd_terrain_f64& terrain, int n, const double* xy, const int* map,
+                                      double* out, hipStream_t stream);
 
 // rescue.hip (srbd_qp_settings.f64_rescue / f32_iters): list the QPs with status >=
 // min_status in batch order, widen / narrow QP-major rows of `elems` values between fp32 and fp64

@@ -14,6 +14,11 @@
 //      fz_max: 2; the feet: 3 per stage, so only a robot row of an even N starts aligned).
 //      Each lane forms the values of its own elements from closed-form integers (the stage,
 //      its phase, the touchdown stage) and the staged poses: no lane walks the schedule.
+// With a terrain on the handle (srbd_qp_srbd_set_terrain_f64) the kernel's other
+// instantiation runs a phase between the two: the wave enumerates each foot's distinct
+// touchdowns of the window (closed form: j_1 + m period), groups of lanes evaluate one touchdown
+// each with one foothold candidate per lane, a segmented argmin over the key (J, q) picks the
+// foothold, and one lane writes (x, y, z) into a table in LDS that phase 2 reads.
 #include "../../include/srbd_qp.h"
 #include "kernels.h"
 
@@ -25,9 +30,25 @@ constexpr int kGaitWaves = 4;      // robots per block ...
 constexpr int kGaitLdsStage = 4;   // ... each with (px, py, cos, sin) per stage in LDS
 constexpr size_t kGaitLdsMax = 64 * 1024;
 
+// Clamped bilinear height of one map (include/srbd_qp.h states the formula): H is [ny][nx].
+__device__ __forceinline__ double terrain_bilinear(const double* H, int nx, int ny, double x0, double y0,
+                                                   double cell, double x, double y) {
+  const double s = fmin(fmax((x - x0) / cell, 0.0), (double)(nx - 1));
+  const double t = fmin(fmax((y - y0) / cell, 0.0), (double)(ny - 1));
+  const int i = min((int)floor(s), nx - 2), j = min((int)floor(t), ny - 2);
+  const double a = s - (double)i, b = t - (double)j;
+  const double* r0 = H + (size_t)j * nx + i;
+  const double* r1 = r0 + nx;
+  return (1.0 - b) * ((1.0 - a) * r0[0] + a * r0[1]) + b * ((1.0 - a) * r1[0] + a * r1[1]);
+}
+
+// entries of one foot's foothold table: the touchdowns j_1 + m period < N + swing, period >= 2
+__host__ __device__ constexpr int gait_table_rows(int N) { return N / 2 + 1; }
+
 struct GaitArgs {
   int batch, N;
   srbd_gait_f64 g;
+  srbd_terrain_f64 t;   // read by the terrain instantiation only
   GaitIo io;
   double dt, Lz;
   const double* Lbody;  // the MODEL role's [batch][3] (NULL: Lz)
@@ -39,13 +60,21 @@ struct FootConst {
   unsigned period, swing, phi0;  // phi0 = (tick + offset) mod period
   double hx, hy;                 // hip + (S dt / 2)(vx, vy)
   double nx, ny, nz;             // foot_now
+  const double* tab;             // terrain: the foot's foothold table in LDS, (x, y, z) per touchdown
 };
+
+// the first touchdown after stage 0: the smallest j >= 1 with (phi0 + j) mod period == swing
+__device__ __forceinline__ unsigned first_touchdown(const FootConst& f) {
+  const unsigned r = (f.swing + f.period - f.phi0) % f.period;
+  return r ? r : f.period;
+}
 
 __device__ __forceinline__ double yaw_at(double yaw, int k, double dwz) { return fma((double)k, dwz, yaw); }
 
 // Element `comp` of foot row k: foot_now while the foot has not left the ground it stands on,
 // else the foothold of the stage's (next or current) touchdown.  (fbx, fby) is the feedback
 // term k_raibert (vm - Rz(yaw_0)(vx, vy)).
+template <bool TERRAIN>
 __device__ __forceinline__ double foot_elem(const FootConst& f, const double* lds, int N, int k, int comp,
                                             double cx, double cy, double p0x, double p0y, double fbx,
                                             double fby, double ground_z) {
@@ -60,6 +89,10 @@ __device__ __forceinline__ double foot_elem(const FootConst& f, const double* ld
       return comp == 0 ? n0 : comp == 1 ? n1 : n2;
     }
   }
+  if constexpr (TERRAIN) {  // the table's row of this touchdown
+    const unsigned m = (unsigned)((unsigned long long)(j - (long long)first_touchdown(f)) / f.period);
+    return f.tab[(size_t)m * 3 + comp];
+  }
   if (comp == 2) return ground_z;
   const int jc = j < N ? (int)j : N;
   const double* st = lds + (size_t)jc * kGaitLdsStage;
@@ -68,6 +101,73 @@ __device__ __forceinline__ double foot_elem(const FootConst& f, const double* ld
   return cy + (st[1] - p0y) + (s * f.hx + c * f.hy) + fby;
 }
 
+// The nominal foothold of the touchdown whose clamped stage is jc (foot_elem's expression).
+__device__ __forceinline__ void nominal_foothold(const FootConst& f, const double* lds, int jc, double cx, double cy,
+                                                 double p0x, double p0y, double fbx, double fby, double& x,
+                                                 double& y) {
+  const double* st = lds + (size_t)jc * kGaitLdsStage;
+  const double c = st[2], s = st[3];
+  x = cx + (st[0] - p0x) + (c * f.hx - s * f.hy) + fbx;
+  y = cy + (st[1] - p0y) + (s * f.hx + c * f.hy) + fby;
+}
+
+// One foot's foothold table.  Groups of `width` lanes (the power of two that holds the
+// (2 search + 1)^2 candidates) take one touchdown each, lane q of the group its candidate q;
+// a butterfly inside the group leaves the smallest key (J, q) in all of its lanes, and the
+// lane that holds the winner writes its foothold.  The wave runs this uniformly: every lane
+// takes part in every shuffle.
+__device__ __forceinline__ void select_footholds(const FootConst& f, const srbd_terrain_f64& t, const double* H,
+                                                 const double* lds, double* tab, int N, int lane, double cx,
+                                                 double cy, double p0x, double p0y, double fbx, double fby,
+                                                 double ground_z) {
+  if (f.swing == 0) return;  // the foot never lands
+  const int side = 2 * t.search + 1, cand = side * side;
+  const int width = t.search == 0 ? 1 : t.search == 1 ? 16 : t.search == 2 ? 32 : 64;
+  const int group = lane / width, q = lane - group * width;
+  const long long j1 = first_touchdown(f), end = (long long)N + f.swing;  // touchdowns j1 + m period < end
+  // at most gait_table_rows(N) for swing < period (the gait's contract); the min keeps a gait
+  // that breaks it inside the table
+  const int count = j1 < end ? (int)min((end - 1 - j1) / f.period + 1, (long long)gait_table_rows(N)) : 0;
+  const int dj = q / side - t.search, di = q - (q / side) * side - t.search;
+  for (int m0 = 0; m0 < count; m0 += kWave / width) {
+    const int m = m0 + group;
+    const bool valid = m < count && q < cand;
+    double J = __builtin_inf(), x = 0.0, y = 0.0;
+    if (valid) {
+      const long long j = j1 + (long long)m * f.period;
+      nominal_foothold(f, lds, j < N ? (int)j : N, cx, cy, p0x, p0y, fbx, fby, x, y);
+      J = 0.0;
+      if (t.search > 0) {
+        x += t.cell * (double)di;
+        y += t.cell * (double)dj;
+        const double h0 = terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, x, y);
+        double rho = fabs(terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, x + t.cell, y) - h0);
+        rho = fmax(rho, fabs(terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, x - t.cell, y) - h0));
+        rho = fmax(rho, fabs(terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, x, y + t.cell) - h0));
+        rho = fmax(rho, fabs(terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, x, y - t.cell) - h0));
+        J = t.cell * t.cell * (double)(di * di + dj * dj) + t.w_rough * (rho * rho);
+      }
+    }
+    double Jb = J;
+    int qb = q;
+    for (int d = width >> 1; d > 0; d >>= 1) {
+      const double Jo = __shfl_xor(Jb, d, kWave);
+      const int qo = __shfl_xor(qb, d, kWave);
+      if (Jo < Jb || (Jo == Jb && qo < qb)) {
+        Jb = Jo;
+        qb = qo;
+      }
+    }
+    if (valid && qb == q) {
+      double* row = tab + (size_t)m * 3;
+      row[0] = x;
+      row[1] = y;
+      row[2] = ground_z + terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, x, y);
+    }
+  }
+}
+
+template <bool TERRAIN>
 __global__ void __launch_bounds__(kWave* kGaitWaves) srbd_gait_kernel(GaitArgs a) {
   extern __shared__ double gait_lds[];
   const int lane = threadIdx.x & (kWave - 1);
@@ -75,7 +175,9 @@ __global__ void __launch_bounds__(kWave* kGaitWaves) srbd_gait_kernel(GaitArgs a
   const long long qp = (long long)blockIdx.x * (blockDim.x >> 6) + wave;
   const bool live = qp < a.batch;  // wave-uniform
   const int N = a.N;
-  double* lds = gait_lds + (size_t)wave * (N + 1) * kGaitLdsStage;
+  // a robot's LDS: the staged poses, then (terrain) the two feet's foothold tables
+  const size_t per_wave = (size_t)(N + 1) * kGaitLdsStage + (TERRAIN ? (size_t)2 * gait_table_rows(N) * 3 : 0);
+  double* lds = gait_lds + (size_t)wave * per_wave;
   double vx = 0.0, vy = 0.0, wz = 0.0, zh = 0.0, yaw0 = 0.0, p0x = 0.0, p0y = 0.0, cx = 0.0, cy = 0.0;
   double vmx = 0.0, vmy = 0.0;
   FootConst ftr{}, ftl{};  // right, left
@@ -147,6 +249,22 @@ __global__ void __launch_bounds__(kWave* kGaitWaves) srbd_gait_kernel(GaitArgs a
     }
   }
   __syncthreads();  // the staged poses are read by other lanes (no wave has left the kernel)
+  const double* H = nullptr;  // the robot's map
+  if constexpr (TERRAIN) {
+    // ---- the footholds of the window's touchdowns, one candidate per lane ----
+    if (live) {
+      H = a.t.height + (size_t)(a.t.map_r ? a.t.map_r[qp] : 0) * a.t.ny * a.t.nx;
+      double* tab = lds + (size_t)(N + 1) * kGaitLdsStage;
+      ftr.tab = tab;
+      ftl.tab = tab + (size_t)gait_table_rows(N) * 3;
+      const double fx = a.g.k_raibert * (vmx - (lds[2] * vx - lds[3] * vy));
+      const double fy = a.g.k_raibert * (vmy - (lds[3] * vx + lds[2] * vy));
+      select_footholds(ftr, a.t, H, lds, tab, N, lane, cx, cy, p0x, p0y, fx, fy, a.g.ground_z);
+      select_footholds(ftl, a.t, H, lds, tab + (size_t)gait_table_rows(N) * 3, N, lane, cx, cy, p0x, p0y, fx, fy,
+                       a.g.ground_z);
+    }
+    __syncthreads();  // the tables are read by other lanes
+  }
   if (!live) return;
   // ---- phase 2: the rows ----
   const double dwz = a.dt * wz;
@@ -162,14 +280,16 @@ __global__ void __launch_bounds__(kWave* kGaitWaves) srbd_gait_kernel(GaitArgs a
       case 5: return lzw;
       case 6: return st[0];
       case 7: return st[1];
-      case 8: return zh;
+      case 8:
+        if constexpr (TERRAIN) return zh + terrain_bilinear(H, a.t.nx, a.t.ny, a.t.x0, a.t.y0, a.t.cell, st[0], st[1]);
+        return zh;
       case 9: return st[2] * vx - st[3] * vy;
       case 10: return st[3] * vx + st[2] * vy;
       default: return 0.0;
     }
   };
   auto foot = [&](const FootConst& fc, int k, int comp) __attribute__((always_inline)) -> double {
-    return foot_elem(fc, lds, N, k, comp, cx, cy, p0x, p0y, fbx, fby, a.g.ground_z);
+    return foot_elem<TERRAIN>(fc, lds, N, k, comp, cx, cy, p0x, p0y, fbx, fby, a.g.ground_z);
   };
   {  // x_ref: 6 (N + 1) double2
     double2* out = reinterpret_cast<double2*>(a.io.x_ref + (size_t)qp * (N + 1) * 12);
@@ -221,10 +341,27 @@ __global__ void __launch_bounds__(kWave* kGaitWaves) srbd_gait_kernel(GaitArgs a
   }
 }
 
+// srbd_qp_srbd_terrain_height_f64: one point per thread
+__global__ void srbd_terrain_height_kernel(srbd_terrain_f64 t, int n, const double* xy, const int* map, double* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* H = t.height + (size_t)(map ? map[i] : 0) * t.ny * t.nx;
+  out[i] = terrain_bilinear(H, t.nx, t.ny, t.x0, t.y0, t.cell, xy[2 * (size_t)i], xy[2 * (size_t)i + 1]);
+}
+
 }  // namespace
 
+hipError_t launch_srbd_terrain_height(const srbd_terrain_f64& terrain, int n, const double* xy, const int* map,
+                                      double* out, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(srbd_terrain_height_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, terrain,
+                     n, xy, map, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_srbd_gait(const srbd_model_params& p, int batch, int N, const srbd_gait_f64& gait,
-                            const GaitIo& io, hipStream_t stream, const srbd_robots_f64* robots) {
+                            const GaitIo& io, hipStream_t stream, const srbd_robots_f64* robots,
+                            const srbd_terrain_f64* terrain) {
   if (batch <= 0) return hipSuccess;
   GaitArgs a{};
   a.batch = batch;
@@ -236,12 +373,19 @@ hipError_t launch_srbd_gait(const srbd_model_params& p, int batch, int N, const 
   a.Lbody = robots ? robots->Lbody : nullptr;
   auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   a.feet16 = N % 2 == 0 && aligned16(io.foot_r) && aligned16(io.foot_l);
-  // four robots per block while their staged poses fit, else one
-  const size_t per_wave = (size_t)(N + 1) * kGaitLdsStage * sizeof(double);
+  const bool with_terrain = terrain && terrain->height;
+  if (with_terrain) a.t = *terrain;
+  // four robots per block while their staged poses (and, with a terrain, their foothold
+  // tables: 56 N + 80 bytes a robot, four up to N = 291, one up to N = 1024) fit, else one
+  const size_t per_wave =
+      ((size_t)(N + 1) * kGaitLdsStage + (with_terrain ? (size_t)2 * gait_table_rows(N) * 3 : 0)) * sizeof(double);
   const int waves = per_wave * kGaitWaves <= kGaitLdsMax ? kGaitWaves : 1;
   if (per_wave * waves > kGaitLdsMax) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((batch + waves - 1) / waves)), block(kWave * waves);
-  hipLaunchKernelGGL(srbd_gait_kernel, grid, block, per_wave * waves, stream, a);
+  if (with_terrain)
+    hipLaunchKernelGGL(srbd_gait_kernel<true>, grid, block, per_wave * waves, stream, a);
+  else
+    hipLaunchKernelGGL(srbd_gait_kernel<false>, grid, block, per_wave * waves, stream, a);
   return hipGetLastError();
 }
 

@@ -100,6 +100,8 @@ struct srbd_qp_handle_s {
   srbd::Buffer roll, roll_plan;
   // srbd_qp_srbd_set_robots_f64: the two roles' pointers (the caller's arrays; all NULL = clear)
   srbd_robots_f64 robots_model{}, robots_plant{};
+  // srbd_qp_srbd_set_terrain_f64: the planner's height maps (height == NULL: none)
+  srbd_terrain_f64 terrain{};
   // settings.f64_rescue: the compact fp64 batch, and that of the cold fp64 re-solve of
   // rescued QPs the continuation left unsolved
   srbd::Buffer resc, resc2;
@@ -1346,6 +1348,39 @@ int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f6
   return SRBD_QP_OK;
 }
 
+int srbd_qp_srbd_set_terrain_f64(srbd_qp_handle h, const srbd_terrain_f64* terrain) {
+  if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
+  if (h->dims.nx != 12 || h->dims.nu != 12) return fail(SRBD_QP_EDIM, "SRBD terrain needs nx = nu = 12");
+  if (!terrain || !terrain->height) {
+    h->terrain = srbd_terrain_f64{};
+    return SRBD_QP_OK;
+  }
+  const srbd_terrain_f64& t = *terrain;
+  if (t.maps < 1) return fail(SRBD_QP_EINVAL, "set_terrain: maps must be at least 1");
+  if (t.nx < 2 || t.ny < 2) return fail(SRBD_QP_EINVAL, "set_terrain: nx and ny must be at least 2");
+  if (!(t.cell > 0.0) || !std::isfinite(t.cell)) return fail(SRBD_QP_EINVAL, "set_terrain: cell must be positive");
+  if (!std::isfinite(t.x0) || !std::isfinite(t.y0)) return fail(SRBD_QP_EINVAL, "set_terrain: x0, y0 must be finite");
+  if (t.search < 0 || t.search > 3) return fail(SRBD_QP_EINVAL, "set_terrain: search must be in 0..3");
+  if (!(t.w_rough >= 0.0) || !std::isfinite(t.w_rough))
+    return fail(SRBD_QP_EINVAL, "set_terrain: w_rough must be non-negative and finite");
+  h->terrain = t;
+  return SRBD_QP_OK;
+}
+
+int srbd_qp_srbd_terrain_height_f64(srbd_qp_handle h, int n, const double* xy, const int* map, double* out,
+                                    void* stream) {
+  if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
+  if (!h->terrain.height) return fail(SRBD_QP_EINVAL, "terrain_height: no terrain is set");
+  if (n < 0) return fail(SRBD_QP_EINVAL, "terrain_height: n must be non-negative");
+  if (n == 0) return SRBD_QP_OK;  // nothing is read: empty arrays may be NULL
+  if (!xy || !out) return fail(SRBD_QP_EINVAL, "NULL argument");
+  hipStream_t strm = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  srbd::DeviceGuard guard(h->device);
+  const hipError_t e = srbd::launch_srbd_terrain_height(h->terrain, n, xy, map, out, strm);
+  if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+  return SRBD_QP_OK;
+}
+
 // The _plan_ entry points hold the checks and the work; the plain ones forward a NULL plan.
 // All of them read the handle's robots (srbd_qp_srbd_set_robots_f64).
 int srbd_qp_srbd_linearize_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
@@ -1581,7 +1616,8 @@ int srbd_qp_srbd_gait_plan_f64(srbd_qp_handle h, int batch, const srbd_model_par
   io.foot_r = foot_r;
   io.foot_l = foot_l;
   io.fz_max = fz_max;
-  const hipError_t e = srbd::launch_srbd_gait(*params, batch, h->dims.N, *gait, io, strm, &h->robots_model);
+  const hipError_t e =
+      srbd::launch_srbd_gait(*params, batch, h->dims.N, *gait, io, strm, &h->robots_model, &h->terrain);
   if (e != hipSuccess) return fail(SRBD_QP_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
   return SRBD_QP_OK;
 }
@@ -1697,7 +1733,7 @@ static int rollout_impl(srbd_qp_handle h, int batch, const srbd_model_params* pa
       gi.foot_log_stride = (long long)T * 6;
       gi.fz_log = gio->fz_log ? gio->fz_log + (size_t)t * 2 : nullptr;
       gi.fz_log_stride = (long long)T * 2;
-      e = srbd::launch_srbd_gait(*params, batch, N, *gait, gi, strm, &h->robots_model);
+      e = srbd::launch_srbd_gait(*params, batch, N, *gait, gi, strm, &h->robots_model, &h->terrain);
       if (e != hipSuccess) return device_error(e, "rollout: ");
     } else if (with_plan) {
       const double* fields[4] = {plan->x_ref, plan->foot_r, plan->foot_l, plan->fz_max};

@@ -30,7 +30,8 @@ import numpy as np
 from .qp import OcpQpBatch
 
 __all__ = ["SrbdParams", "SrbdPlan", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier",
-           "plant_step", "shift_guess", "SrbdGait", "gait_plan"]
+           "plant_step", "shift_guess", "SrbdGait", "gait_plan", "SrbdTerrain",
+           "terrain_height", "foothold_select"]
 
 
 @dataclass(frozen=True)
@@ -311,13 +312,83 @@ class SrbdGait:
     anchor: int = 0
 
 
+@dataclass(frozen=True)
+class SrbdTerrain:
+    """The C-ABI's srbd_terrain_f64, as numpy: height [maps][ny][nx] (or [ny][nx] for one map),
+    sample (j, i) at (x0 + i cell, y0 + j cell); map_r [B] the robots' maps (None: map 0);
+    search in 0..3 and w_rough >= 0 for the foothold selection."""
+    height: object
+    x0: float
+    y0: float
+    cell: float
+    map_r: object = None
+    search: int = 0
+    w_rough: float = 0.0
+
+
+def terrain_height(terrain: SrbdTerrain, xy, map=None):
+    """Height of map `map` (an int array that broadcasts against xy's leading shape; None: map
+    0) at the points xy [...][2]: include/srbd_qp.h's clamped bilinear, operation for operation."""
+    H = np.asarray(terrain.height, dtype=np.float64)
+    H = H[None] if H.ndim == 2 else H
+    ny, nx = H.shape[1], H.shape[2]
+    xy = np.asarray(xy, dtype=np.float64)
+    m = np.zeros(xy.shape[:-1], dtype=np.int64) if map is None else \
+        np.broadcast_to(np.asarray(map, dtype=np.int64), xy.shape[:-1])
+    s = np.minimum(np.maximum((xy[..., 0] - terrain.x0) / terrain.cell, 0.0), float(nx - 1))
+    t = np.minimum(np.maximum((xy[..., 1] - terrain.y0) / terrain.cell, 0.0), float(ny - 1))
+    i = np.minimum(np.floor(s).astype(np.int64), nx - 2)
+    j = np.minimum(np.floor(t).astype(np.int64), ny - 2)
+    a, b = s - i, t - j
+    return (1.0 - b) * ((1.0 - a) * H[m, j, i] + a * H[m, j, i + 1]) + \
+        b * ((1.0 - a) * H[m, j + 1, i] + a * H[m, j + 1, i + 1])
+
+
+def foothold_select(terrain: SrbdTerrain, n, map=None):
+    """The foothold selection of include/srbd_qp.h's terrain for the nominal footholds n
+    [...][2] on map `map`: candidate q = (dj + search)(2 search + 1) + (di + search) lies at
+    n + cell (di, dj) and costs J = cell^2 (di^2 + dj^2) + w_rough rho^2, rho the largest height
+    difference to the four points one cell away; the smallest J wins, ties go to the smallest q.
+    Returns (xy [...][2], z [...] the height there, q [...] the winner, margin [...] the second
+    smallest J minus the smallest; inf with search == 0, where nothing is evaluated)."""
+    n = np.asarray(n, dtype=np.float64)
+    S, cell = int(terrain.search), terrain.cell
+    lead = n.shape[:-1]
+    if S == 0:
+        return n.copy(), terrain_height(terrain, n, map), np.zeros(lead, dtype=np.int64), np.full(lead, np.inf)
+    ex, ey = np.array([cell, 0.0]), np.array([0.0, cell])
+    best = np.full(lead, np.inf)
+    second = np.full(lead, np.inf)
+    qbest = np.zeros(lead, dtype=np.int64)
+    xy = n.copy()
+    q = 0
+    for dj in range(-S, S + 1):
+        for di in range(-S, S + 1):
+            c = n + cell * np.array([float(di), float(dj)])
+            h0 = terrain_height(terrain, c, map)
+            rho = np.abs(terrain_height(terrain, c + ex, map) - h0)
+            rho = np.maximum(rho, np.abs(terrain_height(terrain, c - ex, map) - h0))
+            rho = np.maximum(rho, np.abs(terrain_height(terrain, c + ey, map) - h0))
+            rho = np.maximum(rho, np.abs(terrain_height(terrain, c - ey, map) - h0))
+            J = cell * cell * float(di * di + dj * dj) + terrain.w_rough * (rho * rho)
+            win = J < best  # strictly: a tie stays with the smaller q
+            second = np.where(win, best, np.minimum(second, J))
+            best = np.where(win, J, best)
+            qbest = np.where(win, q, qbest)
+            xy = np.where(win[..., None], c, xy)
+            q += 1
+    return xy, terrain_height(terrain, xy, map), qbest, second - best
+
+
 def gait_plan(p: SrbdParams, gait: SrbdGait, cmd, x, tick: int, ref_pose, foot_now, N: Optional[int] = None,
-              Lbody_z=None):
+              Lbody_z=None, terrain: Optional[SrbdTerrain] = None, map_r=None):
     """One tick's plan window, the statement of include/srbd_qp.h's gait planner: cmd [B][4]
     (vx, vy in the heading frame, wz, body height), x [B][12] the measured state, tick >= 0,
     ref_pose [B][3] (px, py, yaw), foot_now [B][2][3].  N: the horizon (None: p.N); Lbody_z [B]:
-    the robots' Lbody[2] (None: p.Lbody[2]).  Returns (SrbdPlan, new ref_pose, new foot_now);
-    the inputs are left alone."""
+    the robots' Lbody[2] (None: p.Lbody[2]).  terrain: a SrbdTerrain (None: flat ground at
+    gait.ground_z, the planner without terrain); map_r [B]: the robots' maps (None:
+    terrain.map_r, then map 0).  Returns (SrbdPlan, new ref_pose, new foot_now); the inputs
+    are left alone."""
     cmd, x = np.asarray(cmd, dtype=np.float64), np.asarray(x, dtype=np.float64)
     ref_pose, foot_now = np.asarray(ref_pose, dtype=np.float64), np.asarray(foot_now, dtype=np.float64)
     B = cmd.shape[0]
@@ -349,6 +420,11 @@ def gait_plan(p: SrbdParams, gait: SrbdGait, cmd, x, tick: int, ref_pose, foot_n
     x_ref[:, :, 6:8] = pk
     x_ref[:, :, 8] = zh
     x_ref[:, :, 9:11] = vw
+    if terrain is not None:
+        if map_r is None:
+            map_r = terrain.map_r
+        maps = np.zeros(B, dtype=np.int64) if map_r is None else np.asarray(map_r, dtype=np.int64)[:B]
+        x_ref[:, :, 8] = zh + terrain_height(terrain, pk, maps[:, None])
     # contact schedule and feet
     ks = k[:N]
     fz = np.empty((B, N, 2))
@@ -372,6 +448,10 @@ def gait_plan(p: SrbdParams, gait: SrbdGait, cmd, x, tick: int, ref_pose, foot_n
         F[:, :, 0] = c[:, None, 0] + (pj[:, :, 0] - p0[:, None, 0]) + (cj * hx - sj * hy) + fb[:, None, 0]
         F[:, :, 1] = c[:, None, 1] + (pj[:, :, 1] - p0[:, None, 1]) + (sj * hx + cj * hy) + fb[:, None, 1]
         F[:, :, 2] = gait.ground_z
+        if terrain is not None:  # the touchdown moves to the best candidate and takes its height
+            sel_xy, sel_z, _, _ = foothold_select(terrain, F[:, :, 0:2], maps[:, None])
+            F[:, :, 0:2] = sel_xy
+            F[:, :, 2] = gait.ground_z + sel_z
         feet.append(np.where(down[:, :, None], foot_now[:, f, None, :], F))
     plan = SrbdPlan(x_ref=x_ref, foot_r=feet[0], foot_l=feet[1], fz_max=fz)
     new_pose = np.concatenate([pk[:, 1], yaw[:, 1:2]], axis=1)
