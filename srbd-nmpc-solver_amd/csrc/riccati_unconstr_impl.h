@@ -173,6 +173,26 @@ __device__ __forceinline__ void store_riccati_out(const ProblemArgsT<real>& a, i
   }
 }
 
+// ---- the forward sweep's 96-byte rows as whole lines (fp64 large-batch kernel) ----
+// A row of x, u, pi or b is one and a half 64-byte memory requests, and its line's other
+// half moves a stage later, when the line has left L2.  So the rows go through slot A of the
+// wave's image, which is free once stage 0's rows are in registers, in chunks of four stages
+// (384 bytes per QP and vector, aligned to stage indices that are multiples of 4): the
+// groups write their rows of x, u, pi into the slot and the wave stores a full chunk as
+// 16-byte pieces in lane order, as HbmSrc::store_stage copies a record out; b comes in the
+// same way, a chunk ahead of its use, and lane i takes b[i] from the slot.  Offsets in reals
+// from the image base; a vector's chunk of the wave's four QPs is [group][stage & 3][12].
+constexpr int kLineVec = 4 * 4 * 12;                     // 192 reals, 96 pieces of 16 bytes
+constexpr int kLineOut = 0;                              // x, u, pi
+constexpr int kLineB = 3 * kLineVec;                     // b: two chunks, [chunk & 1]
+constexpr int kLinePieces = 4 * 12 * (int)sizeof(real) / 16;  // 24: one QP's chunk of a vector
+static_assert(kLineB + 2 * kLineVec <= 4 * kWsStage, "the line staging fits slot A");
+// The flush stores non-temporally: a chunk is not read again by this kernel, and streaming it
+// past the caches measured faster than plain stores (0: plain stores).
+#ifndef SRBD_RIC_FLUSH_NT
+#define SRBD_RIC_FLUSH_NT 1
+#endif
+
 // ---- forward sweep (row-owned), shared by every unconstrained kernel ----
 // u = K x + k, pi = P x + p, x+ = A x + B u + b (A, B, b row-owned from the QP data: the
 // closed-loop Acl = A + B K is not formed in the backward sweep, which saves it 12 FMA blocks
@@ -194,6 +214,81 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
   real* uo = a.u + (size_t)qp * N * nu;
   real* po = a.pi + (size_t)qp * (N + 1) * nx;
   real Pr[12], Kr[12], Ar[12], pv, kv, bv;
+  // The line staging above (keeps_turnaround only; every other instantiation compiles none of
+  // it).  The wave's live lanes are its first 16 * nq (the kernel has retired the groups past
+  // the batch), so piece p of a vector's chunk, p < 24 * nq, belongs to lane p % (16 * nq).
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(3))) real lds_real;
+  typedef __attribute__((address_space(3))) d2 lds_d2;
+  lds_real* line = nullptr;
+  int gq = 0, qp0 = qp, nq = 1, wl = 0;
+  if constexpr (keeps_turnaround<Src>) {
+    // (line and qp0 are the same in every lane of the wave: held as scalars)
+    line = (lds_real*)(uintptr_t)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_real*)src.img);
+    gq = src.gq;
+    qp0 = __builtin_amdgcn_readfirstlane(qp - gq);
+    nq = a.batch - qp0 < 4 ? a.batch - qp0 : 4;
+    wl = (int)(threadIdx.x & 63);
+  }
+  // the lane's two pieces of a chunk: p = l and l + 16 * nq (the second one of the lower half
+  // of the lanes only); QP group p / 24, piece w = p % 24 of that QP's chunk.  l is the lane
+  // in the wave, made opaque where a chunk moves: everything derived from it is then computed
+  // there and nothing of it stays in registers across the stages.
+  auto piece = [&](int l, int i, int& g, int& w) {
+    const int p = l + i * 16 * nq;
+    g = p / kLinePieces;
+    w = p - g * kLinePieces;
+    return p < nq * kLinePieces;
+  };
+  // chunk c of b, global -> registers -> slot A; stages past N - 1 do not exist
+  auto fetch_b = [&](int c) {
+    int l = wl;
+    opaque(l);
+    lds_d2* dst = (lds_d2*)(line + kLineB + (c & 1) * kLineVec);
+    d2 bq[2];
+    sfor<0, 2>([&](auto i) {
+      constexpr int I = decltype(i)::value;
+      int g, w;
+      bq[I] = d2{0.0, 0.0};
+      if (piece(l, I, g, w) && 4 * c + w / 6 < N) {
+        const HbmSrc o{a, qp0 + g};
+        bq[I] = reinterpret_cast<const d2*>(o.b(4 * c + w / 6))[w % 6];
+      }
+    });
+    sfor<0, 2>([&](auto i) {
+      constexpr int I = decltype(i)::value;
+      int g, w;
+      if (piece(l, I, g, w)) dst[l + I * 16 * nq] = bq[I];
+    });
+    lds_wave_fence();  // other lanes read these pieces
+  };
+  // chunk c of x, u, pi, slot A -> global: rows 4 c .. of each QP, as many as the array has
+  auto flush_out = [&](int c) {
+    lds_wave_fence();  // the pieces are other lanes' rows
+    int l = wl;
+    opaque(l);
+    sfor<0, 2>([&](auto i) {
+      constexpr int I = decltype(i)::value;
+      int g, w;
+      const bool live = piece(l, I, g, w);
+      sfor<0, 3>([&](auto v) {
+        constexpr int V = decltype(v)::value;
+        const int rows = V == 1 ? N : N + 1;
+        real* base = V == 0 ? a.x : V == 1 ? a.u : a.pi;
+        const int left = rows - 4 * c, nr = left < 4 ? left : 4;
+        const lds_d2* from = (const lds_d2*)(line + kLineOut + V * kLineVec);
+        if (live && w < 6 * nr) {
+          d2* to = reinterpret_cast<d2*>(base + ((size_t)(qp0 + g) * rows + 4 * c) * 12) + w;
+          if constexpr (SRBD_RIC_FLUSH_NT) {
+            __builtin_nontemporal_store(from[l + I * 16 * nq], to);
+          } else {
+            *to = from[l + I * 16 * nq];
+          }
+        }
+      });
+    });
+    lds_wave_fence();  // the next chunk's rows stay after these reads
+  };
   auto load_rows = [&](int k, real (&P_)[12], real (&K_)[12], real (&A__)[12], real& p_, real& k_,
                        real& b_) {
     const real* rec = src.rec(k);
@@ -208,7 +303,11 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
         A__[J] = Ab[J * 12 + row];  // column-major block: row `row` at stride 12
       });
       k_ = kr[12];
-      b_ = src.b(k)[row];
+      if constexpr (keeps_turnaround<Src>) {  // (a streamed record there: k >= 2, b staged)
+        b_ = line[kLineB + ((k >> 2) & 1) * kLineVec + (gq * 4 + (k & 3)) * 12 + row];
+      } else {
+        b_ = src.b(k)[row];
+      }
     }
   };
   // The same rows where stage k's record is the one kept in the wave's LDS image (k < N),
@@ -236,6 +335,7 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
   auto kept = [&](int k) { return keeps_turnaround<Src> && k < 2 && k < N; };
   if (kept(0)) {
     load_rows_kept(0, Pr, Kr, Ar, pv, kv, bv);
+    lds_wave_fence();  // slot A is the line staging from here on
   } else {
     load_rows(0, Pr, Kr, Ar, pv, kv, bv);
   }
@@ -247,6 +347,12 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
       const real* Bb = src.B(k);
       sfor<0, 12>([&](auto j) { Br[decltype(j)::value] = Bb[decltype(j)::value * 12 + row]; });
     }
+    // b a chunk ahead, at the end of this stage: chunk 0 (stages 2, 3 of it: 0 and 1 are read
+    // with the kept records) in stage 0, chunk c + 1 in stage 4 c + 1; its stages are read from
+    // stage 4 c + 3 on, and the half of the slot it overwrites held chunk c - 1, last read in
+    // stage 4 c - 2
+    const int fc = k == 0 ? 0 : (k >> 2) + 1;
+    const bool fetch = keeps_turnaround<Src> && (k == 0 || (k & 3) == 1) && 4 * fc < N;
     real Pn[12], Kn[12], An[12], pvn = real(0.0), kvn = real(0.0), bvn = real(0.0);
     if (k < N) {
       if (kept(k + 1)) {
@@ -266,8 +372,13 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
       pp = fmadd(Pr[J], bx[J], pp);
     });
     if (own) {
-      xo[(size_t)k * nx + lane] = xv;
-      po[(size_t)k * nx + lane] = pp;
+      if constexpr (keeps_turnaround<Src>) {
+        line[kLineOut + (gq * 4 + (k & 3)) * 12 + lane] = xv;
+        line[kLineOut + 2 * kLineVec + (gq * 4 + (k & 3)) * 12 + lane] = pp;
+      } else {
+        xo[(size_t)k * nx + lane] = xv;
+        po[(size_t)k * nx + lane] = pp;
+      }
       if (so) {
         so[k * nx + lane] = xv;
         so[(2 * N + 1) * nx + k * nx + lane] = pp;
@@ -281,7 +392,11 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
       xn = fmadd(Ar[J], bx[J], xn);
     });
     if (own) {
-      uo[(size_t)k * nu + lane] = uu;
+      if constexpr (keeps_turnaround<Src>) {
+        line[kLineOut + kLineVec + (gq * 4 + (k & 3)) * 12 + lane] = uu;
+      } else {
+        uo[(size_t)k * nu + lane] = uu;
+      }
       if (so) so[(N + 1) * nx + k * nu + lane] = uu;
     }
     xn = dot_bcast(Br, uu, xn);  // + B u (u element-owned, broadcast inside the FMAs)
@@ -296,7 +411,13 @@ __device__ __forceinline__ void fwd_sweep(const ProblemArgsT<real>& a, const Src
     pv = pvn;
     kv = kvn;
     bv = bvn;
+    // (at the end of the stage, where only the next stage's rows are live)
+    if constexpr (keeps_turnaround<Src>) {
+      if ((k & 3) == 3) flush_out(k >> 2);
+      if (fetch) fetch_b(fc);
+    }
   }
+  if constexpr (keeps_turnaround<Src>) flush_out(N >> 2);  // the last, partial chunk
   if (a.status || a.iter) {
     const unsigned long long m = __ballot(bad);
     const int shift = (threadIdx.x & 63) & ~(kGroup - 1);
