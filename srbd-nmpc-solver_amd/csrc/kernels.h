@@ -1,4 +1,4 @@
-// kernels.h -- launch interface between the C-ABI (srbd_qp_capi.hip) and the
+// kernels.h -- launch interface between the C-ABI (srbd_qp_capi.hip, capi_*.hip) and the
 // HIP kernels.  Internal; not part of the public ABI.
 #pragma once
 
@@ -86,7 +86,7 @@ struct ProblemArgsT {
   const int* qp_list;
   // internal (the latency IPM, ric_alg 1 with lq_fact 1): device word the kernel sets to 1 when a
   // QP's predictor check asks for the LQ factorization (HPIPM's switch), which only the batched
-  // kernels have: the C-ABI then solves the batch there (srbd_qp_capi.hip solve_impl).  (Last:
+  // kernels have: the C-ABI then solves the batch there (capi_solve.hip solve_impl).  (Last:
   // the other fields keep their kernel-argument offsets.)
   int* lat_lq_flag;
 };

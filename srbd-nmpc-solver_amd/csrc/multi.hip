@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/srbd_qp.h"
+#include "capi_handle.h"
 #include "device_guard.h"
 
 struct srbd_qp_multi_s {
@@ -19,10 +20,6 @@ struct srbd_qp_multi_s {
   std::vector<int> dev;
   std::vector<srbd_qp_handle> h;
 };
-
-namespace srbd {
-int set_error(int code, const std::string& msg);  // srbd_qp_capi.hip
-}
 
 extern "C" {
 

@@ -197,5 +197,53 @@ void stage_pointers(const StagePlan& p, char* base, const srbd_qp_dims& m, DataT
   if (sl) for_each_slack_output(m, at, *sl);
 }
 
+// The caller's host arrays against the plan's ranges, in the plan's slot order (d, s, sf and sl
+// as plan_stage got them): fn(host pointer, range) for every non-NULL input ...
+template <class DataT, class Fn>
+void each_staged_input(const StagePlan& p, const srbd_qp_dims& m, const DataT& d, const srbd_qp_soft_f64* sf,
+                       Fn&& fn) {
+  int i = 0;
+  auto visit = [&](size_t, const auto& f) {
+    const StagePlan::Range& g = p.r[i++];
+    if (f) fn(static_cast<const void*>(f), g);
+  };
+  for_each_input(m, visit, d);
+  if (sf) for_each_soft_input(m, visit, *sf);
+}
+
+// ... and fn(host pointer, range, is one of P, p, K, k) for every non-NULL output.  The factors
+// are the solution's slots 3 to 6:
+constexpr int kFactorSlot0 = 3, kFactorSlots = 4;
+namespace detail {
+constexpr bool factor_slots_are_PpKk() {
+  srbd_qp_solution_f64 s{};
+  int i = 0;
+  bool ok = true;
+  auto visit = [&](size_t, auto& f) {
+    const void* member = &f;
+    const bool factor = member == static_cast<const void*>(&s.P) || member == static_cast<const void*>(&s.p) ||
+                        member == static_cast<const void*>(&s.K) || member == static_cast<const void*>(&s.k);
+    ok = ok && factor == (i >= kFactorSlot0 && i < kFactorSlot0 + kFactorSlots);
+    ++i;
+  };
+  for_each_solution_field(srbd_qp_dims{}, 0, visit, visit, s);
+  return ok;
+}
+}  // namespace detail
+static_assert(detail::factor_slots_are_PpKk(), "kFactorSlot0 / kFactorSlots must name P, p, K, k");
+
+template <class SolT, class Fn>
+void each_staged_output(const StagePlan& p, const srbd_qp_dims& m, const SolT& s, const srbd_qp_slack_f64* sl,
+                        Fn&& fn) {
+  int i = p.n_in;
+  auto visit = [&](size_t, const auto& f) {
+    const int slot = i - p.n_in;
+    const StagePlan::Range& g = p.r[i++];
+    if (f) fn(static_cast<void*>(f), g, slot >= kFactorSlot0 && slot < kFactorSlot0 + kFactorSlots);
+  };
+  for_each_solution_field(m, 0, visit, visit, s);
+  if (sl) for_each_slack_output(m, visit, *sl);
+}
+
 }  // namespace fields
 }  // namespace srbd

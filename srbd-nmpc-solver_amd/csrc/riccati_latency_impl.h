@@ -402,7 +402,7 @@ __global__ void __launch_bounds__(kLatThreads, 1) riccati_latency_kernel(Problem
   lat_solve<RES>(a, lds_raw);
 }
 
-// The same solve as a resident server for the one-QP host call (srbd_qp_capi.hip, the
+// The same solve as a resident server for the one-QP host call (capi_host.hip, the
 // reference's call pattern): one workgroup stays on its CU and polls the mailbox in mapped
 // host memory, so a call costs no launch, no dispatch and no completion signal -- the host
 // posts a request number, the kernel solves the QP from the (fixed) staging buffer `a` points

@@ -1,6 +1,7 @@
 // qp_fields_test.cpp -- host-only checks of csrc/qp_fields.h (no GPU): every visitor reaches
 // each pointer member of its struct exactly once, the per-QP counts equal literals written out
-// here, and the staging plan is aligned, disjoint, inputs-first, with x and u adjacent.
+// here, the staging plan is aligned, disjoint, inputs-first, with x and u adjacent, and the
+// walkers of a host-buffer call pair each non-NULL field with its range of that plan.
 #include "../qp_fields.h"
 
 #include <cstdio>
@@ -245,7 +246,83 @@ static void test_stage_plan() {
   CHECK(t.total == p.total + 5 * 512 + 2 * 512);
 }
 
+// The walkers of a host-buffer call: a call with some fields NULL, without and with the soft and
+// slack structs.  They visit exactly the non-NULL fields, in slot order, each with the range
+// that stage_pointers turns into that field's pointer, and flag exactly P, p, K, k.
+struct Visit {
+  const void* host;
+  const void* staged;  // where stage_pointers puts the field
+  bool factor;
+};
+static void test_walkers(bool with_soft) {
+  const srbd_qp_dims m = dims();
+  static double mem[64];  // a distinct host address per field
+  static int imem[2];
+  int next = 0;
+  auto fresh = [&] { return &mem[next++]; };
+  srbd_qp_data_f64 d{};
+  for (const double** p : {&d.A, &d.B, &d.b, &d.Q, &d.S, &d.R, &d.q, &d.r, &d.x0, &d.lbx, &d.ubx, &d.lg, &d.ug})
+    *p = fresh();
+  srbd_qp_solution_f64 s{};
+  for (double** p : {&s.x, &s.u, &s.pi, &s.P, &s.p, &s.k, &s.obj}) *p = fresh();  // no K, res, stat
+  s.iter = imem;                                                                  // no status
+  srbd_qp_soft_f64 sf{};
+  for (const double** p : {&sf.soft_x, &sf.Zl_x, &sf.Zu_x, &sf.zl_x, &sf.zu_x, &sf.lus_x}) *p = fresh();
+  srbd_qp_slack_f64 sl{};
+  for (double** p : {&sl.sl_x, &sl.su_u}) *p = fresh();
+  const srbd_qp_soft_f64* psf = with_soft ? &sf : nullptr;
+  const srbd_qp_slack_f64* psl = with_soft ? &sl : nullptr;
+
+  const f::StagePlan p = f::plan_stage<double>(m, 2, kStatRows, d, s, psf, psl);
+  std::vector<char> base(p.total);
+  srbd_qp_data_f64 dd;
+  srbd_qp_solution_f64 ss;
+  srbd_qp_soft_f64 dsf;
+  srbd_qp_slack_f64 dsl;
+  f::stage_pointers(p, base.data(), m, dd, ss, with_soft ? &dsf : nullptr, with_soft ? &dsl : nullptr);
+
+  // what to expect: the non-NULL fields of the caller's structs, paired with the staged ones
+  std::vector<Visit> want_in, want_out;
+  auto pair_in = [&](size_t, const auto& host, const auto& staged) {
+    if (host) want_in.push_back({host, staged, false});
+  };
+  auto pair_out = [&](size_t, const auto& host, const auto& staged) {
+    const void* v = host;
+    if (host) want_out.push_back({v, staged, v == s.P || v == s.p || v == s.K || v == s.k});
+  };
+  f::for_each_input(m, pair_in, d, dd);
+  if (with_soft) f::for_each_soft_input(m, pair_in, sf, dsf);
+  f::for_each_solution_field(m, kStatRows, pair_out, pair_out, s, ss);
+  if (with_soft) f::for_each_slack_output(m, pair_out, sl, dsl);
+  CHECK(want_in.size() == (with_soft ? 13u + 6u : 13u));
+  CHECK(want_out.size() == (with_soft ? 8u + 2u : 8u));
+
+  std::vector<Visit> got_in, got_out;
+  f::each_staged_input(p, m, d, psf, [&](const void* host, const f::StagePlan::Range& g) {
+    CHECK(g.off != f::kNoOffset && g.off + g.bytes <= p.in_end && g.bytes > 0);
+    got_in.push_back({host, base.data() + g.off, false});
+  });
+  f::each_staged_output(p, m, s, psl, [&](void* host, const f::StagePlan::Range& g, bool factor) {
+    CHECK(g.off != f::kNoOffset && g.off >= p.in_end && g.off + g.bytes <= p.total && g.bytes > 0);
+    got_out.push_back({host, base.data() + g.off, factor});
+  });
+  auto same = [](const std::vector<Visit>& a, const std::vector<Visit>& b) {
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+      if (a[i].host != b[i].host || a[i].staged != b[i].staged || a[i].factor != b[i].factor) return false;
+    return true;
+  };
+  CHECK(same(got_in, want_in));
+  CHECK(same(got_out, want_out));
+  int factors = 0;
+  for (const Visit& v : got_out) factors += v.factor;
+  CHECK(factors == 3);  // P, p, k (K is NULL)
+  CHECK(f::kFactorSlot0 == 3 && f::kFactorSlots == 4);
+}
+
 int main() {
+  test_walkers(false);
+  test_walkers(true);
   test_visits_twins<srbd_qp_data_f64, srbd_qp_solution_f64>();
   test_visits_twins<srbd_qp_data_f32, srbd_qp_solution_f32>();
   test_visits_soft();

@@ -13,7 +13,7 @@ import helpers
 pytestmark = pytest.mark.gpu
 
 OUTPUTS = ("x", "u", "pi", "P", "p", "K", "k", "status", "iter", "res", "obj", "stat")
-PINNED_MAX_BYTES = 8 << 20  # kPinnedMaxBytes (srbd_qp_capi.hip)
+PINNED_MAX_BYTES = 8 << 20  # kPinnedMaxBytes (capi_host.hip)
 
 
 def _host_solve(capi, qp, x0, st, dtype=np.float64, x_init=None, u_init=None):

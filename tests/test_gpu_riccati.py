@@ -597,7 +597,7 @@ def test_resident_server_leaves_other_streams_running(pkg, monkeypatch):
     back kernels of other streams: HIP maps streams onto a few hardware queues (4 per process
     here) that process their packets in order, so a kernel queued behind the resident server
     on a shared queue would wait until the server leaves.  The server's stream is created so
-    that it does not share a queue with other streams (srbd_qp_capi.hip server_launch); here a
+    that it does not share a queue with other streams (capi_host.hip server_launch); here a
     small kernel on each of 8 fresh torch streams, and on torch's default stream, finishes
     within 50 ms while the server keeps serving; so does one on each of 2 high-priority streams,
     which may share the server's queue but wait at most its 20 ms lifetime."""
