@@ -522,14 +522,17 @@ typedef struct srbd_advance_f64 {
  *     continuous model (SRBDModel::GetContinuousDynamic) with the feet of stage 0 of
  *     plan->foot_r / foot_l, or params->foot_* where that field or the plan is NULL; w adds
  *     wrench[0:3] to rows 3..5 (the angular-momentum rate) and wrench[3:6] / mass to rows
- *     9..11.  The plant applies u0 as it is: it clamps nothing and applies no fz_max.
+ *     9..11.  The plant applies u0 as it is: it clamps nothing and applies no fz_max -- unless
+ *     a contact model is set on the handle (srbd_qp_srbd_set_contact_f64 below), which
+ *     replaces this step and step 1's u0 by its own statement.
  *  3. New last stage: xN = one RK4 step of the model over dt from the old xs[N] with the old
  *     us[N-1] and the feet of the plan's stage N-1, no wrench: the shifted guess has zero
  *     shooting defect at its last stage.
  *  4. Shift: xs[k] <- xs[k+1] for k = 0..N-1, then xs[N] <- xN; us[k] <- us[k+1] for
  *     k = 0..N-2, us[N-1] stays.  Shifted entries are bit copies.  xs[0] is the old xs[1], not
  *     x: the step forms x0 - xs[:, 0] itself (NMPC_solver.cpp:320).
- * `plan` is this tick's window (may be NULL); only its feet are read.
+ * `plan` is this tick's window (may be NULL); only its feet are read (and, with a contact
+ * model, row 0 of fz_max).
  * Checks: NULL h / params / adv / xs / us and substeps < 1 are SRBD_QP_EINVAL; the handle
  * needs nx = nu = 12 (SRBD_QP_EDIM); batch above the capacity is SRBD_QP_ECAPACITY;
  * batch == 0 returns SRBD_QP_OK.                                                    */
@@ -729,8 +732,8 @@ int srbd_qp_srbd_rollout_gait_f64(srbd_qp_handle h, int batch, const srbd_model_
  * Checks: NULL handle, maps < 1, nx or ny < 2, cell not > 0, search outside 0..3, w_rough < 0
  * or not finite, x0 or y0 not finite are SRBD_QP_EINVAL; a handle without nx = nu = 12 is
  * SRBD_QP_EDIM.
- * Out of scope: a plant that knows the ground (it applies u0 at the planned foot, wherever
- * that is), swing clearance and swing trajectories, a vertical-velocity or tilt reference on
+ * Out of scope: the ground under the plant (that is the contact model's own true ground,
+ * srbd_qp_srbd_set_contact_f64), swing clearance and swing trajectories, a vertical-velocity or tilt reference on
  * slopes, one private map per robot (the map index covers it), srbd_qp_multi_*, the
  * hpipm-cpp shim, fp32.
  * ---------------------------------------------------------------------- */
@@ -750,6 +753,86 @@ int srbd_qp_srbd_set_terrain_f64(srbd_qp_handle h, const srbd_terrain_f64* terra
  * set, n < 0 and, for n > 0, a NULL xy or out are SRBD_QP_EINVAL; n == 0 returns SRBD_QP_OK. */
 int srbd_qp_srbd_terrain_height_f64(srbd_qp_handle h, int n, const double* xy /*[n][2]*/,
                                     const int* map /*[n], NULL = 0*/, double* out /*[n]*/, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Contact model and fall detection (additive to ABI 12): what the plant of
+ * srbd_qp_srbd_advance_f64, and so of both rollouts, does to the commanded input before it
+ * integrates it, and what it reports per robot.  Without a contact the plant applies us[0] as it
+ * is; with one, a foot can only push, only while the schedule has it on the ground, only inside
+ * the TRUE friction cone and moment limits, and it stands on the TRUE ground, which may differ
+ * from the map the planner believes in (srbd_qp_srbd_set_terrain_f64).  A fall detector freezes
+ * fallen robots and counts the plant steps each robot survived.
+ * The call attaches to the handle like set_robots / set_terrain: it copies the struct and does
+ * no device work; contact == NULL clears it, and with the contact cleared every call launches
+ * the kernels it launched before and gives the same bits.  It is read by the plant step of
+ * srbd_qp_srbd_advance_f64, srbd_qp_srbd_rollout_f64 and srbd_qp_srbd_rollout_gait_f64 issued
+ * afterwards, and by nothing else: the controller (linearisation, line search, NMPC step, the
+ * model step that makes the new xs[N]) never sees it.  A call without a plant state (x == NULL:
+ * shift only) does not read it either.  The arrays are device memory with at least `batch`
+ * rows, read and written by the launched kernels: keep them alive until those have finished.
+ *
+ * Plant step of robot i with a contact set (step 2 of srbd_qp_srbd_advance_f64), with u = us[0],
+ * clamp(v, lo, hi) = fmin(fmax(v, lo), hi), mu_i = mu_r ? mu_r[i] : mu, and u' the applied input
+ * (u_applied, the rollout's u_log):
+ *  1. Already fallen (fallen != NULL and fallen[i] != 0 on entry): x keeps its bits, u' is
+ *     twelve zeros, alive[i] and sat[i] are unchanged.  The shift of xs / us runs as always.
+ *  2. Non-finite input: if any of the twelve entries of u is not finite the robot falls now:
+ *     fallen[i] = 1 (when given), x keeps its bits, u' is twelve zeros, alive[i] and sat[i] are
+ *     unchanged.  (With fallen == NULL finite inputs are the caller's contract.)
+ *  3. Contact flags: foot f (0 right, 1 left) is in contact, c_f, iff the plan's
+ *     fz_max[0][f] > fz_contact; without a plan, or with plan->fz_max == NULL, both feet are.
+ *  4. Projection, per foot f (o = 6 f), each bound ONE multiplication, nothing fused:
+ *       fz'    = c_f ? clamp(u[o+2], 0, fz_hi) : 0
+ *       b      = mu_i * fz'
+ *       fx'    = clamp(u[o], -b, b),   fy' = clamp(u[o+1], -b, b)
+ *       tau_a' = clamp(u[o+3+a], -(Lt_a * fz'), Lt_a * fz')   for a = x, y, z (Ltx, Lty, Ltz)
+ *     (the sign of a zero result is not specified).
+ *  5. sat: bit 4 f + kind is OR-ed into sat[i] iff the projected values of that group differ
+ *     (!=) from the commanded ones:
+ *       kind 0  fz' != u[o+2] and (not c_f, or fz' > u[o+2]): raised to 0, or zeroed by swing
+ *       kind 1  c_f and fz' < u[o+2]: lowered to fz_hi
+ *       kind 2  fx' != u[o] or fy' != u[o+1]
+ *       kind 3  tau_a' != u[o+3+a] for some a
+ *  6. Feet: with ground.height set, a foot in contact stands at (planned x, planned y,
+ *     ground_z + h_true(x, y)), h_true the clamped bilinear of srbd_terrain_f64 above on map
+ *     ground.map_r[i] (NULL: map 0); a foot not in contact, and every foot without
+ *     ground.height, stays at the planned point (the plan's stage 0, or params->foot_*).
+ *  7. Integration: x <- the `substeps` RK4 steps of srbd_qp_srbd_advance_f64 with u', those feet,
+ *     the wrench, and the PLANT role's mass and inertia.
+ *  8. Fall test on the new state, only when fallen is given.  The robot falls (fallen[i] = 1) if
+ *       any entry of x is not finite -- then x keeps its bits of before the step; or
+ *       x[8] - (ground_z + h_true(x[6], x[7])) < z_min   (h_true = 0 without ground.height); or
+ *       expm(x[0:3])[2][2] < cos_tilt_min.
+ *     A robot that falls on a finite state keeps that state.  alive[i] += 1 iff the robot is
+ *     not fallen after this step.
+ * Checks: a NULL handle; mu negative or not finite where mu_r is NULL; an Lt* negative or not
+ * finite; fz_hi NaN or <= 0 (+inf is allowed); fz_contact negative or not finite; ground_z or
+ * z_min not finite; cos_tilt_min outside [-1, 1]; alive without fallen; and, with ground.height
+ * given, set_terrain's checks of maps, nx, ny, cell, x0, y0 are SRBD_QP_EINVAL; a handle
+ * without nx = nu = 12 is SRBD_QP_EDIM.  ground.search / ground.w_rough are ignored.
+ * Caller's contract (device data, not checked): mu_r finite and >= 0, map indices in range.
+ * Out of scope: feet that slide when friction saturates (the foot stays where the plan put it);
+ * any body-ground collision; skipping the NMPC step of fallen robots (they are still stepped,
+ * their plant is frozen); re-arming a fallen robot inside a rollout (the caller resets x and
+ * fallen between rollouts); srbd_qp_multi_*, the hpipm-cpp shim, fp32.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_contact_f64 {
+  double mu;              /* plant friction coefficient of every robot where mu_r is NULL      */
+  const double* mu_r;     /* device [batch], optional                                          */
+  double Ltx, Lty, Ltz;   /* |tau_a| <= Lt_a * fz per foot; the model's own rows are (0, Lfx, Lfz) */
+  double fz_hi;           /* largest normal force a foot in contact can take; > 0, +inf allowed */
+  double fz_contact;      /* foot f is in contact this tick iff the plan's fz_max[0][f] > fz_contact;
+                             without a plan or without fz_max both feet are in contact          */
+  double ground_z;        /* as srbd_gait_f64.ground_z                                          */
+  srbd_terrain_f64 ground;/* the TRUE ground; height == NULL: flat at ground_z and the feet keep
+                             their planned z.  search / w_rough are ignored.                    */
+  double z_min;           /* fall: body height above the true ground under it < z_min           */
+  double cos_tilt_min;    /* fall: expm(x[0:3])[2][2] < cos_tilt_min                            */
+  int* fallen;            /* device [batch] in/out, optional; NULL = no fall detection          */
+  int* alive;             /* device [batch] in/out, optional (needs fallen): plant steps survived */
+  unsigned* sat;          /* device [batch] in/out, optional: OR of the limits that were active */
+} srbd_contact_f64;
+int srbd_qp_srbd_set_contact_f64(srbd_qp_handle h, const srbd_contact_f64* contact);
 
 /* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,

@@ -262,6 +262,72 @@ class Terrain:
         return ts
 
 
+class ContactStruct(C.Structure):
+    """srbd_contact_f64."""
+    _fields_ = [("mu", C.c_double), ("mu_r", _dp), ("Ltx", C.c_double), ("Lty", C.c_double), ("Ltz", C.c_double),
+                ("fz_hi", C.c_double), ("fz_contact", C.c_double), ("ground_z", C.c_double),
+                ("ground", TerrainStruct), ("z_min", C.c_double), ("cos_tilt_min", C.c_double), ("fallen", _dp),
+                ("alive", _dp), ("sat", _dp)]
+
+
+class Contact:
+    """The plant's contact model and fall detection for Handle.set_contact (srbd_contact_f64;
+    include/srbd_qp.h states the plant step with it).  mu: the true friction coefficient, or
+    mu_r, a torch fp64 device tensor [B]; Lt = (Ltx, Lty, Ltz): |tau_a| <= Lt_a fz per foot; fz_hi:
+    the largest normal force of a foot in contact (inf allowed); fz_contact: foot f is in contact
+    iff the plan's fz_max[:, 0, f] exceeds it; ground: a Terrain, the TRUE ground under the feet
+    (None: flat at ground_z, the feet keep their planned z; its search / w_rough are ignored);
+    z_min, cos_tilt_min: the fall thresholds on the body's height above the true ground and on
+    expm(x[0:3])[2][2].  fallen, alive: int32 device tensors [B], sat: a uint32 (or int32) device
+    tensor [B]; all three optional and in/out (alive needs fallen): zero them before a rollout.
+    Dtype, contiguity, shapes and device are checked here, with ValueError; the numbers by the
+    library.  The holder keeps the tensors alive."""
+
+    def __init__(self, mu=0.5, mu_r=None, Lt=(0.0, 0.05, 0.05), fz_hi=float("inf"), fz_contact=0.0, ground_z=0.0,
+                 ground: Optional["Terrain"] = None, z_min=0.0, cos_tilt_min=0.0, fallen=None, alive=None,
+                 sat=None):
+        self.mu, self.mu_r, self.Lt, self.fz_hi, self.fz_contact = mu, mu_r, Lt, fz_hi, fz_contact
+        self.ground_z, self.ground, self.z_min, self.cos_tilt_min = ground_z, ground, z_min, cos_tilt_min
+        self.fallen, self.alive, self.sat = fallen, alive, sat
+        self.rows = None
+
+    def struct(self, device=None) -> ContactStruct:
+        import torch
+        if len(self.Lt) != 3:
+            raise ValueError(f"contact.Lt needs three values (x, y, z), got {len(self.Lt)}")
+        cs = ContactStruct()
+        cs.mu, cs.fz_hi, cs.fz_contact = float(self.mu), float(self.fz_hi), float(self.fz_contact)
+        cs.Ltx, cs.Lty, cs.Ltz = (float(v) for v in self.Lt)
+        cs.ground_z, cs.z_min, cs.cos_tilt_min = float(self.ground_z), float(self.z_min), float(self.cos_tilt_min)
+        rows = []
+        kinds = (("mu_r", (torch.float64,), "torch.float64"), ("fallen", (torch.int32,), "torch.int32"),
+                 ("alive", (torch.int32,), "torch.int32"),
+                 ("sat", (getattr(torch, "uint32", torch.int32), torch.int32), "torch.uint32 or torch.int32"))
+        for name, dtypes, text in kinds:
+            t = getattr(self, name)
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+                raise ValueError(f"contact.{name} must be a {text} tensor")
+            if t.dim() != 1 or t.shape[0] < 1:
+                raise ValueError(f"contact.{name} has shape {tuple(t.shape)}, expected (B,)")
+            if not t.is_contiguous():
+                raise ValueError(f"contact.{name} must be contiguous")
+            if t.device.type != "cuda" or (device is not None and t.device != device):
+                raise ValueError(f"contact.{name} is on {t.device}, the handle on "
+                                 f"{device if device is not None else 'a GPU'}")
+            rows.append(int(t.shape[0]))
+            setattr(cs, name, t.data_ptr())
+        if self.alive is not None and self.fallen is None:
+            raise ValueError("contact.alive needs contact.fallen")
+        if self.ground is not None:
+            cs.ground = self.ground.struct(device)
+            if self.ground.rows is not None:
+                rows.append(self.ground.rows)
+        self.rows = min(rows) if rows else None
+        return cs
+
+
 class AdvanceStruct(C.Structure):
     """srbd_advance_f64."""
     _fields_ = [("substeps", C.c_int), ("wrench", _dp)]
@@ -471,6 +537,9 @@ def lib():
             L.srbd_qp_srbd_set_terrain_f64.restype = C.c_int
             L.srbd_qp_srbd_terrain_height_f64.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
             L.srbd_qp_srbd_terrain_height_f64.restype = C.c_int
+        if hasattr(L, "srbd_qp_srbd_set_contact_f64"):  # the contact model (older builds: A/B runs)
+            L.srbd_qp_srbd_set_contact_f64.argtypes = [C.c_void_p, C.POINTER(ContactStruct)]
+            L.srbd_qp_srbd_set_contact_f64.restype = C.c_int
         if hasattr(L, "srbd_qp_srbd_gait_plan_f64"):  # the gait planner (older builds: A/B runs)
             L.srbd_qp_srbd_gait_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
                                                      C.POINTER(GaitStruct), C.c_void_p, C.c_void_p,
@@ -631,6 +700,20 @@ class Handle:
         check(lib().srbd_qp_srbd_set_terrain_f64(self._h, None if ts is None else C.byref(ts)),
               "srbd_qp_srbd_set_terrain_f64")
         self._terrain = terrain
+
+    def set_contact(self, contact: Optional["Contact"] = None) -> None:
+        """srbd_qp_srbd_set_contact_f64: the plant step of srbd_advance, srbd_rollout and
+        srbd_rollout_gait on this handle afterwards projects the commanded input onto what the
+        feet can transmit (unilateral, the schedule's contacts, the Contact's friction and moment
+        limits), stands the feet on the Contact's true ground, and records falls, survived ticks
+        and the limits that were active in the Contact's tensors.  The controller never sees it.
+        None clears it: the plant as it was, bit for bit.  The handle keeps the Contact, and so
+        its tensors, alive until it is replaced."""
+        import torch
+        cs = None if contact is None else contact.struct(torch.device("cuda", self.device))
+        check(lib().srbd_qp_srbd_set_contact_f64(self._h, None if cs is None else C.byref(cs)),
+              "srbd_qp_srbd_set_contact_f64")
+        self._contact = contact
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -819,6 +902,14 @@ def _check_terrain(handle, B) -> None:
         raise ValueError(f"the handle's terrain has a map_r of {t.rows} rows, the batch {int(B)}")
 
 
+def _check_contact(handle, B) -> None:
+    """The handle's contact (Handle.set_contact) is read and written at rows 0..B-1: ValueError if
+    one of its tensors has fewer."""
+    c = getattr(handle, "_contact", None)
+    if c is not None and c.rows is not None and c.rows < int(B):
+        raise ValueError(f"the handle's contact has tensors of {c.rows} rows, the batch {int(B)}")
+
+
 def _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream):
     """srbd_qp_srbd_linearize_f64, or the _plan_ entry point when a plan is given."""
     tail = (SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()), C.c_void_p(us.data_ptr()),
@@ -960,7 +1051,9 @@ def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wr
     steps of dt / substeps with u0, stage 0's feet of `plan` (this tick's window) and the
     external wrench [B][6] (torque, force; None: none); xs [B][N+1][12], us [B][N][12] shifted
     by one stage in place, the new last stage one model step from the old one.  Asynchronous on
-    the handle's stream, ordered like a torch op.  Returns u0 [B][12] (a device tensor)."""
+    the handle's stream, ordered like a torch op.  Returns u0 [B][12] (a device tensor).  With a
+    contact on the handle (Handle.set_contact) and a plant state, the plant applies the
+    projection of u0 and the returned tensor holds that: what was really applied."""
     import torch
     B, N = us.shape[0], us.shape[1]
     dev = xs.device
@@ -972,6 +1065,7 @@ def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wr
         _check_f64("wrench", wrench, (B, 6), dev)
     plan_ref = _plan_ref(plan, B, N, dev)
     _check_robots(handle, B)
+    _check_contact(handle, B)
     u0 = torch.empty(B, 12, dtype=torch.float64, device=dev)
     adv = AdvanceStruct(int(substeps), _tensor_ptr(wrench) or None)
     p = params or default_model_params()
@@ -1010,6 +1104,7 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
     P = N + T - 1 if plan_stages is None else int(plan_stages)
     plan_ref = _plan_ref(plan, B, P, dev)
     _check_robots(handle, B)
+    _check_contact(handle, B)
     rows = max(T, 0)
     x_log = torch.zeros(B, rows + 1, 12, dtype=torch.float64, device=dev)
     u_log = torch.zeros(B, rows, 12, dtype=torch.float64, device=dev)
@@ -1100,6 +1195,7 @@ def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pos
     gs = gait.struct(B, dev)
     _check_robots(handle, B)
     _check_terrain(handle, B)
+    _check_contact(handle, B)
     f = dict(dtype=torch.float64, device=dev)
     x_log = torch.zeros(B, rows + 1, 12, **f)
     u_log = torch.zeros(B, rows, 12, **f)

@@ -76,6 +76,10 @@ struct srbd_qp_handle_s {
   srbd_robots_f64 robots_model{}, robots_plant{};
   // srbd_qp_srbd_set_terrain_f64: the planner's height maps (height == NULL: none)
   srbd_terrain_f64 terrain{};
+  // srbd_qp_srbd_set_contact_f64: the plant's contact model and fall detection (a copy of the
+  // caller's struct; has_contact false: none)
+  srbd_contact_f64 contact{};
+  bool has_contact = false;
   // settings.f64_rescue: the compact fp64 batch, and that of the cold fp64 re-solve of
   // rescued QPs the continuation left unsolved
   srbd::Buffer resc, resc2;

@@ -1,5 +1,5 @@
 // capi_srbd.hip -- the SRBD entry points of the C-ABI (include/srbd_qp.h, srbd_qp_srbd_*):
-// robots and terrain, linearisation, line search, the NMPC step, the plant step, the gait
+// robots, terrain and the plant's contact model, linearisation, line search, the NMPC step, the plant step, the gait
 // planner and the closed-loop rollout.
 #include "capi_handle.h"
 
@@ -72,6 +72,21 @@ int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f6
   return SRBD_QP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// the checks of a height map's grid that set_terrain and set_contact (its true ground) share
+int check_grid(const srbd_terrain_f64& t, const std::string& who) {
+  if (t.maps < 1) return fail(SRBD_QP_EINVAL, who + ": maps must be at least 1");
+  if (t.nx < 2 || t.ny < 2) return fail(SRBD_QP_EINVAL, who + ": nx and ny must be at least 2");
+  if (!(t.cell > 0.0) || !std::isfinite(t.cell)) return fail(SRBD_QP_EINVAL, who + ": cell must be positive");
+  if (!std::isfinite(t.x0) || !std::isfinite(t.y0)) return fail(SRBD_QP_EINVAL, who + ": x0, y0 must be finite");
+  return SRBD_QP_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int srbd_qp_srbd_set_terrain_f64(srbd_qp_handle h, const srbd_terrain_f64* terrain) {
   if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
   if (h->dims.nx != 12 || h->dims.nu != 12) return fail(SRBD_QP_EDIM, "SRBD terrain needs nx = nu = 12");
@@ -80,10 +95,7 @@ int srbd_qp_srbd_set_terrain_f64(srbd_qp_handle h, const srbd_terrain_f64* terra
     return SRBD_QP_OK;
   }
   const srbd_terrain_f64& t = *terrain;
-  if (t.maps < 1) return fail(SRBD_QP_EINVAL, "set_terrain: maps must be at least 1");
-  if (t.nx < 2 || t.ny < 2) return fail(SRBD_QP_EINVAL, "set_terrain: nx and ny must be at least 2");
-  if (!(t.cell > 0.0) || !std::isfinite(t.cell)) return fail(SRBD_QP_EINVAL, "set_terrain: cell must be positive");
-  if (!std::isfinite(t.x0) || !std::isfinite(t.y0)) return fail(SRBD_QP_EINVAL, "set_terrain: x0, y0 must be finite");
+  if (const int rc = check_grid(t, "set_terrain")) return rc;
   if (t.search < 0 || t.search > 3) return fail(SRBD_QP_EINVAL, "set_terrain: search must be in 0..3");
   if (!(t.w_rough >= 0.0) || !std::isfinite(t.w_rough))
     return fail(SRBD_QP_EINVAL, "set_terrain: w_rough must be non-negative and finite");
@@ -102,6 +114,34 @@ int srbd_qp_srbd_terrain_height_f64(srbd_qp_handle h, int n, const double* xy, c
   srbd::DeviceGuard guard(h->device);
   const hipError_t e = srbd::launch_srbd_terrain_height(h->terrain, n, xy, map, out, strm);
   if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
+  return SRBD_QP_OK;
+}
+
+int srbd_qp_srbd_set_contact_f64(srbd_qp_handle h, const srbd_contact_f64* contact) {
+  if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
+  if (h->dims.nx != 12 || h->dims.nu != 12) return fail(SRBD_QP_EDIM, "the SRBD contact model needs nx = nu = 12");
+  if (!contact) {
+    h->contact = srbd_contact_f64{};
+    h->has_contact = false;
+    return SRBD_QP_OK;
+  }
+  const srbd_contact_f64& c = *contact;
+  auto bound = [](double v) { return v >= 0.0 && std::isfinite(v); };  // (false for a NaN)
+  if (!c.mu_r && !bound(c.mu)) return fail(SRBD_QP_EINVAL, "set_contact: mu must be non-negative and finite");
+  if (!bound(c.Ltx) || !bound(c.Lty) || !bound(c.Ltz))
+    return fail(SRBD_QP_EINVAL, "set_contact: Ltx, Lty, Ltz must be non-negative and finite");
+  if (!(c.fz_hi > 0.0)) return fail(SRBD_QP_EINVAL, "set_contact: fz_hi must be positive");
+  if (!bound(c.fz_contact)) return fail(SRBD_QP_EINVAL, "set_contact: fz_contact must be non-negative and finite");
+  if (!std::isfinite(c.ground_z) || !std::isfinite(c.z_min))
+    return fail(SRBD_QP_EINVAL, "set_contact: ground_z and z_min must be finite");
+  if (!(c.cos_tilt_min >= -1.0 && c.cos_tilt_min <= 1.0))
+    return fail(SRBD_QP_EINVAL, "set_contact: cos_tilt_min must be in [-1, 1]");
+  if (c.alive && !c.fallen) return fail(SRBD_QP_EINVAL, "set_contact: alive needs fallen");
+  if (c.ground.height) {
+    if (const int rc = check_grid(c.ground, "set_contact: ground")) return rc;
+  }
+  h->contact = c;
+  h->has_contact = true;
   return SRBD_QP_OK;
 }
 
@@ -329,7 +369,7 @@ int srbd_qp_srbd_advance_f64(srbd_qp_handle h, int batch, const srbd_model_param
   srbd::DeviceGuard guard(h->device);
   const srbd::AdvanceIo io = advance_io(adv->substeps, xs, us, x, adv->wrench, u_applied, 0, 1);
   const hipError_t e = srbd::launch_srbd_advance(*params, batch, h->dims.N, io, plan, strm, &h->robots_model,
-                                                 &h->robots_plant);
+                                                 &h->robots_plant, h->has_contact ? &h->contact : nullptr);
   if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
   return SRBD_QP_OK;
 }
@@ -495,7 +535,8 @@ static int rollout_impl(srbd_qp_handle h, int batch, const srbd_model_params* pa
     io.it_log = roll->sqp_iter_log ? roll->sqp_iter_log + t : nullptr;
     io.cv_log = roll->converged_log ? roll->converged_log + t : nullptr;
     io.log_stride = T;
-    e = srbd::launch_srbd_advance(*params, batch, N, io, wplan, strm, &h->robots_model, &h->robots_plant);
+    e = srbd::launch_srbd_advance(*params, batch, N, io, wplan, strm, &h->robots_model, &h->robots_plant,
+                                  h->has_contact ? &h->contact : nullptr);
     if (e != hipSuccess) return hip_fail(alloc_code(e), "rollout: ", e);
   }
   e = hipStreamSynchronize(strm);

@@ -269,10 +269,14 @@ struct AdvanceIo {
 };
 // `robots`: the handle's MODEL role (lane 1, and lane 0 where the PLANT role has no value);
 // `plant`: its PLANT role (lane 0: mass and Lbody).  Either may be NULL.
+// `contact`: the handle's contact model (srbd_qp_srbd_set_contact_f64); NULL, or a call without
+// a plant state (io.x == NULL: shift only), is the kernel without it, the instantiations of
+// before.  With a contact the plan's fz_max row 0 is read beside the feet.
 hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, const AdvanceIo& io,
                                const srbd_plan_f64* plan, hipStream_t stream,
                                const srbd_robots_f64* robots = nullptr,
-                               const srbd_robots_f64* plant = nullptr);
+                               const srbd_robots_f64* plant = nullptr,
+                               const srbd_contact_f64* contact = nullptr);
 // Up to four strided row copies, dst[r * dstride + e] = src[r * sstride + e] (e < width,
 // r < batch), and alpha[r] = alpha_value when alpha is given, in one launch.
 struct RolloutRow {

@@ -21,6 +21,7 @@
 // foothold, and one lane writes (x, y, z) into a table in LDS that phase 2 reads.
 #include "../../include/srbd_qp.h"
 #include "kernels.h"
+#include "srbd_terrain.h"
 
 namespace srbd {
 namespace {
@@ -29,18 +30,6 @@ constexpr int kWave = 64;
 constexpr int kGaitWaves = 4;      // robots per block ...
 constexpr int kGaitLdsStage = 4;   // ... each with (px, py, cos, sin) per stage in LDS
 constexpr size_t kGaitLdsMax = 64 * 1024;
-
-// Clamped bilinear height of one map (include/srbd_qp.h states the formula): H is [ny][nx].
-__device__ __forceinline__ double terrain_bilinear(const double* H, int nx, int ny, double x0, double y0,
-                                                   double cell, double x, double y) {
-  const double s = fmin(fmax((x - x0) / cell, 0.0), (double)(nx - 1));
-  const double t = fmin(fmax((y - y0) / cell, 0.0), (double)(ny - 1));
-  const int i = min((int)floor(s), nx - 2), j = min((int)floor(t), ny - 2);
-  const double a = s - (double)i, b = t - (double)j;
-  const double* r0 = H + (size_t)j * nx + i;
-  const double* r1 = r0 + nx;
-  return (1.0 - b) * ((1.0 - a) * r0[0] + a * r0[1]) + b * ((1.0 - a) * r1[0] + a * r1[1]);
-}
 
 // entries of one foot's foothold table: the touchdowns j_1 + m period < N + swing, period >= 2
 __host__ __device__ constexpr int gait_table_rows(int N) { return N / 2 + 1; }

@@ -2,7 +2,9 @@
 // (srbd_qp_srbd_advance_f64 / srbd_qp_srbd_rollout_f64):
 //   srbd_advance_kernel   per robot: the applied input u0 = us[0], the plant's RK4 steps from x
 //                         with u0 (and an external wrench), the new last stage of the guess and
-//                         the in-place shift of xs / us by one stage;
+//                         the in-place shift of xs / us by one stage; with a contact model
+//                         (srbd_contact_f64) u0 is first projected onto what the
+//                         feet can transmit, and fallen robots are frozen;
 //   rollout_rows_kernel   strided row copies: the gather of one tick's plan window out of a
 //                         plan longer than the horizon, x_log[:, 0], and the per-tick alpha.
 // The model is srbd_model.h's, the one the linearisation and the line search evaluate.  The host
@@ -10,6 +12,7 @@
 #include "../../include/srbd_qp.h"
 #include "kernels.h"
 #include "srbd_model.h"
+#include "srbd_terrain.h"
 
 namespace srbd {
 namespace {
@@ -40,8 +43,16 @@ struct AdvRobots {
   const double *plant_mass, *plant_Lbody;  // lane 0
 };
 struct NoAdvRobots {};
-template <bool PLAN, bool ROBOT>
-struct AdvArgsT : AdvArgs, PlanArgs<PLAN>, std::conditional_t<ROBOT, AdvRobots, NoAdvRobots> {};
+// With a contact: the handle's srbd_contact_f64, read by lane 0 only.
+struct AdvContact {
+  srbd_contact_f64 c;
+};
+struct NoAdvContact {};
+template <bool PLAN, bool ROBOT, bool CONTACT>
+struct AdvArgsT : AdvArgs,
+                  PlanArgs<PLAN>,
+                  std::conditional_t<ROBOT, AdvRobots, NoAdvRobots>,
+                  std::conditional_t<CONTACT, AdvContact, NoAdvContact> {};
 
 // `steps` classical RK4 steps of length h of xdot = f(x, u) + w from x (in place).  With has_w,
 // w adds wr[0:3] to rows 3..5 and wr[3:6] / mass to rows 9..11 of every slope.  The slopes
@@ -84,6 +95,104 @@ __device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, const Rb
   }
 }
 
+// The model step of lanes 0 and 1 with a contact (srbd_contact_f64; include/srbd_qp.h states the
+// plant step operation for operation, srbd_model.py's plant_step(contact=...) restates it).
+// Lane 1 takes no part in the contact: it runs rk4_steps on its own inputs as without one.  Lane
+// 0 projects its input u in place onto what the feet can transmit (u then is the applied input),
+// moves the feet in contact onto the true ground, integrates, and tests the new state for a
+// fall; a robot that has fallen, or whose input is not finite, runs zero RK4 steps, so its x
+// keeps its bits.  Each bound of the projection is one multiplication and nothing is added to
+// it, so no operation is fused and the host statement agrees to the bit.  `xin` is the plant
+// state in memory (not yet overwritten), `h` the RK4 step length.  Both lanes go through one
+// call site of rk4_steps, with the feet as values (lane 0's may have moved).
+template <bool PLAN, class Args, class Rb>
+__device__ __forceinline__ void contact_step(const Model& m, const Args& a, const StageVals<PLAN>& sv, const Rb& rb,
+                                             long long qp, bool plant, const double* xin, double (&xv)[12],
+                                             double (&u)[12], const double (&wr)[6], bool has_w, double h,
+                                             int steps) {
+  const srbd_model_params& p = m.p;
+  const srbd_contact_f64& c = a.c;
+  StageVals<true> sc;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    sc.fr[i] = sv.foot_r(p, i);
+    sc.fl[i] = sv.foot_l(p, i);
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f) sc.fz[f] = sv.fz_max(p, f);
+  const srbd_terrain_f64& g = c.ground;
+  const double* H = nullptr;  // lane 0: the robot's map of the true ground
+  bool test = false;          // lane 0: the robot stood on entry and its input is finite
+  if (plant) {
+    const bool frozen = c.fallen && c.fallen[qp] != 0;
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) finite = finite && __builtin_isfinite(u[i]);
+    if (frozen || !finite) {
+      if (!frozen && c.fallen) c.fallen[qp] = 1;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) u[i] = 0.0;
+      steps = 0;
+    } else {
+      const double mu = c.mu_r ? c.mu_r[qp] : c.mu;
+      bool on[2] = {true, true};  // the contact flags
+      if constexpr (PLAN) {
+        if (a.fz_max) {
+          on[0] = sc.fz[0] > c.fz_contact;
+          on[1] = sc.fz[1] > c.fz_contact;
+        }
+      }
+      const double Lt[3] = {c.Ltx, c.Lty, c.Ltz};
+      unsigned sat = 0;
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        const int o = 6 * f;
+        const double fz = u[o + 2];
+        const double fzp = on[f] ? fmin(fmax(fz, 0.0), c.fz_hi) : 0.0;
+        const double b = mu * fzp;
+        const double fxp = fmin(fmax(u[o], -b), b), fyp = fmin(fmax(u[o + 1], -b), b);
+        if (fzp != fz) sat |= ((!on[f] || fzp > fz) ? 1u : 2u) << (4 * f);
+        if (fxp != u[o] || fyp != u[o + 1]) sat |= 4u << (4 * f);
+        bool torque = false;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          const double bt = Lt[t] * fzp;
+          const double tp = fmin(fmax(u[o + 3 + t], -bt), bt);
+          torque = torque || tp != u[o + 3 + t];
+          u[o + 3 + t] = tp;
+        }
+        if (torque) sat |= 8u << (4 * f);
+        u[o] = fxp;
+        u[o + 1] = fyp;
+        u[o + 2] = fzp;
+      }
+      if (c.sat && sat) c.sat[qp] |= sat;
+      if (g.height) {
+        H = g.height + (size_t)(g.map_r ? g.map_r[qp] : 0) * g.ny * g.nx;
+        if (on[0]) sc.fr[2] = c.ground_z + terrain_bilinear(H, g.nx, g.ny, g.x0, g.y0, g.cell, sc.fr[0], sc.fr[1]);
+        if (on[1]) sc.fl[2] = c.ground_z + terrain_bilinear(H, g.nx, g.ny, g.x0, g.y0, g.cell, sc.fl[0], sc.fl[1]);
+      }
+      test = c.fallen != nullptr;
+    }
+  }
+  rk4_steps(m, sc, rb, xv, u, wr, has_w, h, steps);
+  if (test) {
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) finite = finite && __builtin_isfinite(xv[i]);
+    bool fell = true;
+    if (!finite) {  // the state of before the step
+#pragma unroll
+      for (int i = 0; i < 12; ++i) xv[i] = xin[i];
+    } else {
+      const double hg = H ? terrain_bilinear(H, g.nx, g.ny, g.x0, g.y0, g.cell, xv[6], xv[7]) : 0.0;
+      fell = xv[8] - (c.ground_z + hg) < c.z_min || expm(seg(xv, 0)).a[2][2] < c.cos_tilt_min;
+    }
+    if (fell) c.fallen[qp] = 1;
+    else if (c.alive) c.alive[qp] += 1;
+  }
+}
+
 // One wave per robot.
 //   Lane 0 is the plant: u0 = us[0] (also written to u_out), x <- `substeps` RK4 steps of
 //   dt / substeps with u0, the wrench and stage 0's feet.  Lane 1 is the new last stage:
@@ -108,8 +217,14 @@ __device__ __forceinline__ void rk4_steps(const Model& m, const St& sv, const Rb
 // instructions.
 // Rows are multiples of 96 bytes and the shift is 96 bytes, so the double2 accesses stay 16-byte
 // aligned (the entry point checks the base pointers), adjacent lanes on adjacent 16 bytes.
-template <bool PLAN, bool ROBOT>
-__global__ void __launch_bounds__(kWave* kAdvWaves) srbd_advance_kernel(Model m, AdvArgsT<PLAN, ROBOT> a) {
+//
+// CONTACT (a contact model on the handle, and a plant state to step): lane 0's step is
+// contact_step's -- a few min / max, up to three samples of the true ground and the fall test,
+// all while lane 1 waits masked, as it already does through lane 0's substeps.  The lanes, the
+// whole-wave shift and the barriers are as without; CONTACT = false is the code without.
+template <bool PLAN, bool ROBOT, bool CONTACT>
+__global__ void __launch_bounds__(kWave* kAdvWaves)
+    srbd_advance_kernel(Model m, AdvArgsT<PLAN, ROBOT, CONTACT> a) {
   const int lane = threadIdx.x & (kWave - 1);
   const long long qp = (long long)blockIdx.x * kAdvWaves + (threadIdx.x >> 6);
   if (qp >= a.batch) return;  // wave-uniform
@@ -143,7 +258,10 @@ __global__ void __launch_bounds__(kWave* kAdvWaves) srbd_advance_kernel(Model m,
         for (int i = 0; i < 6; ++i) wr[i] = a.wrench[(size_t)qp * a.wrench_stride + i];
       }
       const int steps = plant ? a.substeps : 1;
-      rk4_steps(m, sv, rb, xv, u, wr, has_w, p.dt / (double)steps, steps);
+      if constexpr (CONTACT)
+        contact_step<PLAN>(m, a, sv, rb, qp, plant, xin, xv, u, wr, has_w, p.dt / (double)steps, steps);
+      else
+        rk4_steps(m, sv, rb, xv, u, wr, has_w, p.dt / (double)steps, steps);
     }
     if (plant) {
       if (a.u_out) {
@@ -225,7 +343,7 @@ __global__ void __launch_bounds__(256) rollout_rows_kernel(RowsArgs a) {
 
 hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, const AdvanceIo& io,
                                const srbd_plan_f64* plan, hipStream_t stream, const srbd_robots_f64* robots,
-                               const srbd_robots_f64* plant) {
+                               const srbd_robots_f64* plant, const srbd_contact_f64* contact) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
   AdvArgs a{};
@@ -256,20 +374,28 @@ hipError_t launch_srbd_advance(const srbd_model_params& p, int batch, int N, con
   }
   if (plant && plant->mass) r.plant_mass = plant->mass;
   if (plant && plant->Lbody) r.plant_Lbody = plant->Lbody;
-  const bool with_plan = plan && (plan->foot_r || plan->foot_l);
+  // a contact is read by the plant step only: without a plant state it is the kernel without.
+  // With it the contact flags come from the plan's fz_max, so a plan of fz_max alone is a plan
+  const bool with_contact = contact && io.x;
+  const bool with_plan = plan && (plan->foot_r || plan->foot_l || (with_contact && plan->fz_max));
   const bool with_robots = r.model_mass || r.model_Lbody || r.plant_mass || r.plant_Lbody;
-  auto launch = [&](auto PL, auto RB) {
-    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value;
-    AdvArgsT<kP, kR> full;
+  auto launch = [&](auto PL, auto RB, auto CT) {
+    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value, kC = decltype(CT)::value;
+    AdvArgsT<kP, kR, kC> full;
     static_cast<AdvArgs&>(full) = a;
     if constexpr (kP) static_cast<srbd_plan_f64&>(full) = *plan;
     if constexpr (kR) static_cast<AdvRobots&>(full) = r;
-    hipLaunchKernelGGL((srbd_advance_kernel<kP, kR>), grid, block, 0, stream, m, full);
+    if constexpr (kC) full.c = *contact;
+    hipLaunchKernelGGL((srbd_advance_kernel<kP, kR, kC>), grid, block, 0, stream, m, full);
   };
-  if (with_plan && with_robots) launch(std::true_type{}, std::true_type{});
-  else if (with_plan) launch(std::true_type{}, std::false_type{});
-  else if (with_robots) launch(std::false_type{}, std::true_type{});
-  else launch(std::false_type{}, std::false_type{});
+  auto pick = [&](auto CT) {
+    if (with_plan && with_robots) launch(std::true_type{}, std::true_type{}, CT);
+    else if (with_plan) launch(std::true_type{}, std::false_type{}, CT);
+    else if (with_robots) launch(std::false_type{}, std::true_type{}, CT);
+    else launch(std::false_type{}, std::false_type{}, CT);
+  };
+  if (with_contact) pick(std::true_type{});
+  else pick(std::false_type{});
   return hipGetLastError();
 }
 

@@ -31,7 +31,7 @@ from .qp import OcpQpBatch
 
 __all__ = ["SrbdParams", "SrbdPlan", "generate_batch", "build_qp", "sample_trajectories", "shooting_dynamics", "friction_cone", "barrier",
            "plant_step", "shift_guess", "SrbdGait", "gait_plan", "SrbdTerrain",
-           "terrain_height", "foothold_select"]
+           "terrain_height", "foothold_select", "SrbdContact", "contact_flags", "contact_project", "fall_values"]
 
 
 @dataclass(frozen=True)
@@ -263,18 +263,131 @@ def _rk4_step(x, u, p: SrbdParams, h: float, plan: Optional[SrbdPlan], wrench=No
     return x + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
 
 
-def plant_step(x, u, p: SrbdParams, foot_r=None, foot_l=None, wrench=None, substeps: int = 1):
+def contact_flags(contact: "SrbdContact", fz_max0, B: int):
+    """The contact flags [B][2] of one tick: foot f is in contact iff the plan's fz_max[:, 0, f]
+    (fz_max0 [B][2]) exceeds contact.fz_contact; without it (None) both feet are."""
+    if fz_max0 is None:
+        return np.ones((B, 2), dtype=bool)
+    return np.asarray(fz_max0, dtype=np.float64) > contact.fz_contact
+
+
+def contact_project(u, contact: "SrbdContact", in_contact, mu):
+    """The projection of include/srbd_qp.h's contact model, operation for operation: the
+    commanded input u [B][12] onto what the feet can transmit, with the contact flags in_contact
+    [B][2] and the plant's friction coefficient mu (a float or [B]).  Per foot f (o = 6 f):
+    fz' = c_f ? clamp(fz, 0, fz_hi) : 0;  fx', fy' clamped to +-(mu fz');  tau_a' to +-(Lt_a fz');
+    clamp(v, lo, hi) = fmin(fmax(v, lo), hi), each bound one multiplication.  Returns (u' [B][12],
+    sat [B] uint32): bit 4 f + kind is set iff that group's projected values differ from the
+    commanded ones -- kind 0: fz raised to 0 or zeroed by swing, 1: fz lowered to fz_hi, 2: fx or
+    fy, 3: a torque."""
+    u = np.asarray(u, dtype=np.float64)
+    B = u.shape[0]
+    on = np.broadcast_to(np.asarray(in_contact, dtype=bool), (B, 2))
+    mu = np.broadcast_to(np.asarray(mu, dtype=np.float64), (B,))
+    clamp = lambda v, lo, hi: np.fmin(np.fmax(v, lo), hi)
+    out = np.empty_like(u)
+    sat = np.zeros(B, dtype=np.uint32)
+    for f in range(2):
+        o = 6 * f
+        fz = u[:, o + 2]
+        fzp = np.where(on[:, f], clamp(fz, 0.0, contact.fz_hi), 0.0)
+        b = mu * fzp
+        out[:, o] = clamp(u[:, o], -b, b)
+        out[:, o + 1] = clamp(u[:, o + 1], -b, b)
+        out[:, o + 2] = fzp
+        for a in range(3):
+            bt = contact.Lt[a] * fzp
+            out[:, o + 3 + a] = clamp(u[:, o + 3 + a], -bt, bt)
+        differs = out[:, o:o + 6] != u[:, o:o + 6]
+        kinds = (differs[:, 2] & (~on[:, f] | (fzp > fz)), on[:, f] & (fzp < fz),
+                 differs[:, 0] | differs[:, 1], differs[:, 3:6].any(axis=1))
+        for kind, hit in enumerate(kinds):
+            sat |= np.where(hit, np.uint32(1 << (4 * f + kind)), np.uint32(0))
+    return out, sat
+
+
+def fall_values(x, contact: "SrbdContact", map_r=None):
+    """What the fall test of the contact model compares, for the states x [B][12] on the true
+    ground's maps map_r ([B]; None: contact.ground.map_r, then map 0): (x[8] - (ground_z +
+    h_true(x[6], x[7])), expm(x[0:3])[2][2]), h_true = 0 without a true ground.  A robot falls
+    where the first is below contact.z_min or the second below contact.cos_tilt_min."""
+    x = np.asarray(x, dtype=np.float64)
+    hg = 0.0
+    if contact.ground is not None:
+        m = contact.ground.map_r if map_r is None else map_r
+        hg = terrain_height(contact.ground, x[:, 6:8], None if m is None else np.asarray(m)[:x.shape[0]])
+    return x[:, 8] - (contact.ground_z + hg), expm(x[:, 0:3])[:, 2, 2]
+
+
+def plant_step(x, u, p: SrbdParams, foot_r=None, foot_l=None, wrench=None, substeps: int = 1,
+               contact: Optional["SrbdContact"] = None, in_contact=None, state=None):
     """The plant over one control tick: x [B][12] after `substeps` RK4 steps of dt / substeps of
     xdot = f(x, u) + w with the input u [B][12] held (applied as it is: nothing is clamped).
     foot_r / foot_l [B][3]: the feet during the tick (None: SrbdParams'); wrench [B][6]: an
-    external torque and force on the body, world frame, held over the tick (None: none)."""
+    external torque and force on the body, world frame, held over the tick (None: none).
+
+    contact (a SrbdContact): the plant step of include/srbd_qp.h's contact model, with the
+    contact flags in_contact [B][2] (None: both feet; contact_flags makes them from the plan) and
+    state = {"fallen": [B] int, "alive": [B] int, "sat": [B] uint32}, each optional (None: {}).
+    Returns (x', u', state'): u' the applied input, state' new arrays; the inputs are left alone.
+    A robot already fallen, or whose u is not finite, keeps x and applies zeros; the others apply
+    contact_project(u), stand their feet in contact on the true ground, integrate, and are
+    tested for a fall (only with "fallen" in the state)."""
     if substeps < 1:
         raise ValueError("substeps must be at least 1")
-    feet = None if foot_r is None and foot_l is None else SrbdPlan(foot_r=foot_r, foot_l=foot_l)
     h = p.dt / substeps
-    for _ in range(substeps):
-        x = _rk4_step(x, u, p, h, feet, wrench)
-    return x
+    if contact is None:
+        feet = None if foot_r is None and foot_l is None else SrbdPlan(foot_r=foot_r, foot_l=foot_l)
+        for _ in range(substeps):
+            x = _rk4_step(x, u, p, h, feet, wrench)
+        return x
+    x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    B = x.shape[0]
+    state = {k: np.array(v) for k, v in (state or {}).items() if v is not None}
+    if "alive" in state and "fallen" not in state:
+        raise ValueError("alive needs fallen")
+    on = np.ones((B, 2), dtype=bool) if in_contact is None else np.broadcast_to(np.asarray(in_contact, dtype=bool), (B, 2))
+    mu = np.broadcast_to(np.asarray(contact.mu if contact.mu_r is None else np.asarray(contact.mu_r)[:B],
+                                    dtype=np.float64), (B,))
+    frozen = state["fallen"] != 0 if "fallen" in state else np.zeros(B, dtype=bool)
+    bad = ~frozen & ~np.isfinite(u).all(axis=1)
+    if "fallen" in state:
+        state["fallen"][bad] = 1
+    go = ~frozen & ~bad
+    x_new, u_app = x.copy(), np.zeros_like(u)
+    if not go.any():
+        return x_new, u_app, state
+    up, bits = contact_project(u[go], contact, on[go], mu[go])
+    u_app[go] = up
+    if "sat" in state:
+        state["sat"][go] |= bits.astype(state["sat"].dtype)
+    n = int(go.sum())
+    fr = np.tile(np.array(p.foot_r, dtype=np.float64), (n, 1)) if foot_r is None else np.array(foot_r, dtype=np.float64)[go]
+    fl = np.tile(np.array(p.foot_l, dtype=np.float64), (n, 1)) if foot_l is None else np.array(foot_l, dtype=np.float64)[go]
+    maps = None
+    if contact.ground is not None:
+        g = contact.ground
+        maps = np.zeros(B, dtype=np.int64) if g.map_r is None else np.asarray(g.map_r, dtype=np.int64)[:B]
+        for f, ft in enumerate((fr, fl)):
+            z = contact.ground_z + terrain_height(g, ft[:, 0:2], maps[go])
+            ft[:, 2] = np.where(on[go][:, f], z, ft[:, 2])
+    feet = SrbdPlan(foot_r=fr, foot_l=fl)
+    xg = x[go]
+    w = None if wrench is None else np.asarray(wrench, dtype=np.float64)[go]
+    with np.errstate(all="ignore"):
+        for _ in range(substeps):
+            xg = _rk4_step(xg, up, p, h, feet, w)
+        if "fallen" in state:
+            finite = np.isfinite(xg).all(axis=1)
+            xg[~finite] = x[go][~finite]
+            above, r33 = fall_values(xg, contact, None if maps is None else maps[go])
+            fell = ~finite | (above < contact.z_min) | (r33 < contact.cos_tilt_min)
+            idx = np.nonzero(go)[0]
+            state["fallen"][idx[fell]] = 1
+            if "alive" in state:
+                state["alive"][idx[~fell]] += 1
+    x_new[go] = xg
+    return x_new, u_app, state
 
 
 def shift_guess(xs, us, p: SrbdParams, plan: Optional[SrbdPlan] = None):
@@ -324,6 +437,23 @@ class SrbdTerrain:
     map_r: object = None
     search: int = 0
     w_rough: float = 0.0
+
+
+@dataclass(frozen=True)
+class SrbdContact:
+    """The C-ABI's srbd_contact_f64, as numpy: the plant's contact model and fall thresholds.
+    mu: the true friction coefficient of every robot, or mu_r [B]; Lt = (Ltx, Lty, Ltz); ground: a
+    SrbdTerrain, the TRUE ground with its own map_r (None: flat at ground_z, the feet keep their
+    planned z).  The fallen / alive / sat arrays are plant_step's `state`."""
+    mu: float = 0.5
+    mu_r: object = None
+    Lt: Tuple[float, float, float] = (0.0, 0.05, 0.05)
+    fz_hi: float = math.inf
+    fz_contact: float = 0.0
+    ground_z: float = 0.0
+    ground: Optional[SrbdTerrain] = None
+    z_min: float = 0.0
+    cos_tilt_min: float = 0.0
 
 
 def terrain_height(terrain: SrbdTerrain, xy, map=None):

@@ -1,0 +1,426 @@
+"""The plant's contact model and fall detection on the device (srbd_qp_srbd_set_contact_f64)
+against the host statement srbd_model.plant_step(contact=...): x at the rollout suite's tolerance,
+the applied input, sat, fallen and alive exactly.  A cleared contact, a generous one, a robot
+fallen on entry and non-finite inputs against the plain advance (bit for bit where the header
+says so), and both rollouts against the caller's own loop (bit for bit) and the host closed loop
+of tests/contact_host.py.
+
+The fall thresholds are compared on values that carry rounding: every test that compares a fall
+with the host asserts, on the host result, that each tested robot's height above the ground and
+R33 lie at least 1e-6 from their thresholds.  The seeds and thresholds were chosen on the CPU so
+that this holds; the conditions are asserts, never skips."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+import contact_host as CH
+import robots_host as RB
+import rollout_host as RH
+import terrain_host as TH
+from test_gpu_gait import caller_loop as gait_caller_loop, device_gait
+from test_gpu_plan import NMPC, SQP_MAX_LOOP, _dev, device_plan, handle
+from test_gpu_rollout import D_T, STEP_ATOL_U, STEP_ATOL_X, caller_loop, feet_plan, start
+from test_gpu_terrain import device_terrain
+
+pytestmark = pytest.mark.gpu
+
+B9 = 9  # four robots per block: two full blocks and a tail block of one
+FALL_MARGIN = 1e-6
+STATE = ("fallen", "alive", "sat")
+
+
+def close(got, want, what):  # tests/test_gpu_rollout.py:46, the rollout suite's tolerance for the same RK4
+    np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-11, atol=1e-12 * max(np.abs(want).max(), 1.0),
+                               err_msg=str(what))
+
+
+def device_contact(capi, c, state=None):
+    """(capi.Contact of a srbd_model.SrbdContact, the device state): `state` as contact_host's
+    dicts (None: no arrays); sat travels as int32, the same 32 bits."""
+    import torch
+    st = {k: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).cuda() for k, v in (state or {}).items()}
+    return capi.Contact(mu=c.mu, mu_r=None if c.mu_r is None else _dev(np.asarray(c.mu_r, dtype=np.float64)),
+                        Lt=c.Lt, fz_hi=c.fz_hi, fz_contact=c.fz_contact, ground_z=c.ground_z,
+                        ground=None if c.ground is None else device_terrain(capi, c.ground), z_min=c.z_min,
+                        cos_tilt_min=c.cos_tilt_min, **st), st
+
+
+def state_of(st):
+    """The device state as contact_host's dict (sat back as uint32)."""
+    return {k: v.cpu().numpy().astype(np.uint32 if k == "sat" else np.int32) for k, v in st.items()}
+
+
+def same_state(got, want, what):
+    assert set(got) == set(want), what
+    for k in want:
+        assert np.array_equal(got[k], np.asarray(want[k]).astype(got[k].dtype)), (what, k, got[k], want[k])
+
+
+def true_ground(sm, B, seed):
+    """Two rough maps of 5 x 6 around the robots and their feet, with a per-robot map index."""
+    H = np.stack([TH.rough(5, 6, seed, 0.06), TH.rough(5, 6, seed + 1, 0.04)])
+    return sm.SrbdTerrain(height=H, x0=-0.3, y0=-0.4, cell=0.2, map_r=np.arange(B) % 2)
+
+
+def advance_case(sm, N, seed):
+    """The inputs of the advance tests: nine robots whose us[0] breaks every limit somewhere
+    (robot 0: the right foot pulls and the left exceeds fz_hi; robot 1 the other way round),
+    robot 2 too low and robot 3 tilted too far, a plan whose row 0 has robot 4's right and robot
+    5's left foot in swing, true robots (the PLANT role), a wrench and a true ground."""
+    B = B9
+    p = sm.SrbdParams()
+    xs, us, x = start(sm, p, B, N, seed)
+    rng = np.random.default_rng(seed + 1)
+    u0 = np.empty((B, 2, 6))
+    u0[..., 0:2] = rng.uniform(-60.0, 60.0, size=(B, 2, 2))
+    u0[..., 2] = rng.uniform(20.0, 150.0, size=(B, 2))
+    u0[..., 3:6] = rng.uniform(-6.0, 6.0, size=(B, 2, 3))
+    u0[0, :, 2] = (-10.0, 250.0)
+    u0[1, :, 2] = (250.0, -10.0)
+    us[:, 0] = u0.reshape(B, 12)
+    x[2, 8] = 0.3
+    x[3, 0] = 1.3
+    plan = feet_plan(sm, p, B, N, seed + 2)
+    plan.fz_max[4, 0, 0] = 1.0
+    plan.fz_max[5, 0, 1] = 1.0
+    plant = RB.draw_plant([p] * B, seed + 3)
+    wrench = rng.uniform(-20.0, 20.0, size=(B, 6))
+    contact = sm.SrbdContact(mu=0.4, mu_r=rng.uniform(0.05, 0.9, size=B), Lt=(0.0, 0.04, 0.07), fz_hi=180.0,
+                             fz_contact=5.0, ground_z=0.02, ground=true_ground(sm, B, seed + 4), z_min=0.6,
+                             cos_tilt_min=0.5)
+    return p, xs, us, x, plan, plant, wrench, contact
+
+
+def host_advance(sm, p, xs, us, x, plan, plant, wrench, contact, substeps, state):
+    """One tick on the host: (x', u', state', xs', us', tested) -- tested: the robots whose new
+    state went through the fall test."""
+    B = x.shape[0]
+    on = sm.contact_flags(contact, None if plan is None or plan.fz_max is None else plan.fz_max[:, 0], B)
+    x1, ua, st = CH.plant_step(sm, plant if plant is not None else p, x, us[:, 0], None if plan is None else plan.foot_r[:, 0],
+                               None if plan is None else plan.foot_l[:, 0], wrench, substeps, contact=contact,
+                               in_contact=on, state=state)
+    xs1, us1 = sm.shift_guess(xs, us, p, plan)
+    frozen = state["fallen"] != 0 if state and "fallen" in state else np.zeros(B, dtype=bool)
+    tested = ~frozen & np.isfinite(us[:, 0]).all(axis=1) & np.isfinite(x1).all(axis=1)
+    return x1, ua, st, xs1, us1, tested
+
+
+def assert_fall_margins(sm, contact, x1, tested, what):
+    """No tested robot is closer than FALL_MARGIN to a fall threshold (an assert on the host)."""
+    above, r33 = sm.fall_values(x1, contact)
+    mh, mt = np.abs(above - contact.z_min)[tested], np.abs(r33 - contact.cos_tilt_min)[tested]
+    assert tested.any() and mh.min() >= FALL_MARGIN and mt.min() >= FALL_MARGIN, (what, mh.min(), mt.min())
+    return above, r33
+
+
+def device_advance(capi, h, xs, us, x, plan_t, wrench, substeps):
+    xs_t, us_t, x_t = _dev(xs), _dev(us), _dev(x)
+    u0 = capi.srbd_advance(h, xs_t, us_t, x=x_t, plan=plan_t, wrench=None if wrench is None else _dev(wrench),
+                           substeps=substeps)
+    h.synchronize()
+    return xs_t, us_t, x_t, u0
+
+
+# ---- 1. one tick against the host statement ----
+# N = 3: the shortest horizon with an interior shift; N = 11: 66 double2, the first that needs two chunks.
+@pytest.mark.parametrize("N", [3, 11])
+def test_advance_with_a_contact_matches_the_host_statement(pkg, N):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B = B9
+    p, xs, us, x, plan, plant, wrench, contact = advance_case(sm, N, 900 + N)
+    plan_t = device_plan(capi, plan)
+    pa = RB.arrays(plant, RB.PLANT_FIELDS)
+    plant_t = capi.Robots(mass=_dev(pa["mass"]), Lbody=_dev(pa["Lbody"]))
+    h = handle(capi, N, B, "none")
+    bits, by_height, by_tilt = 0, 0, 0
+    for substeps in (1, 3):
+        for use_plan in (True, False):
+            for use_plant in (True, False):
+                for use_ground in (True, False):
+                    case = (N, substeps, use_plan, use_plant, use_ground)
+                    c = contact if use_ground else dataclasses.replace(contact, ground=None)
+                    state = CH.zero_state(B)
+                    want = host_advance(sm, p, xs, us, x, plan if use_plan else None, plant if use_plant else None,
+                                        wrench, c, substeps, state)
+                    x1, ua, st, xs1, us1, tested = want
+                    above, r33 = assert_fall_margins(sm, c, x1, tested, case)
+                    bits |= int(np.bitwise_or.reduce(st["sat"]))
+                    by_height += int((above[tested] < c.z_min).sum())
+                    by_tilt += int((r33[tested] < c.cos_tilt_min).sum())
+                    h.set_robots(plant=plant_t if use_plant else None)
+                    ct, st_t = device_contact(capi, c, state)
+                    h.set_contact(ct)
+                    xs_t, us_t, x_t, u0 = device_advance(capi, h, xs, us, x, plan_t if use_plan else None, wrench,
+                                                         substeps)
+                    assert np.array_equal(u0.cpu().numpy(), ua), case
+                    same_state(state_of(st_t), st, case)
+                    close(x_t, x1, case)
+                    assert torch.equal(xs_t[:, :N], _dev(xs[:, 1:])) and torch.equal(us_t, _dev(us1)), case
+                    close(xs_t[:, N], xs1[:, N], case)
+    # every branch ran: each of the eight limit bits on some robot, a fall by height, a fall by tilt
+    assert bits == 0xFF and by_height > 0 and by_tilt > 0, (hex(bits), by_height, by_tilt)
+
+
+# ---- 2. set, then cleared: the handle that never had a contact ----
+@pytest.mark.parametrize("N", [3, 11])
+def test_a_cleared_contact_is_the_plant_without_bit_for_bit(pkg, N):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B = B9
+    p, xs, us, x, plan, plant, wrench, contact = advance_case(sm, N, 900 + N)
+    plan_t = device_plan(capi, plan)
+    never = device_advance(capi, handle(capi, N, B, "none"), xs, us, x, plan_t, wrench, 3)
+    h = handle(capi, N, B, "none")
+    ct, st_t = device_contact(capi, contact, CH.zero_state(B))
+    h.set_contact(ct)
+    felt = device_advance(capi, h, xs, us, x, plan_t, wrench, 3)
+    assert not torch.equal(felt[3], never[3]) and not torch.equal(felt[2], never[2])  # a contact is felt ...
+    h.set_contact(None)  # ... and cleared again
+    for name, u, v in zip(("xs", "us", "x", "u_applied"), device_advance(capi, h, xs, us, x, plan_t, wrench, 3), never):
+        assert torch.equal(u, v), name
+    assert bool(st_t["sat"].any())  # (the run with the contact wrote its state; the cleared one nothing more)
+    before = state_of(st_t)
+    device_advance(capi, h, xs, us, x, plan_t, wrench, 3)
+    same_state(state_of(st_t), before, "cleared")
+
+
+# ---- 3. limits that never bind, no fall detection ----
+@pytest.mark.parametrize("N", [3, 11])
+def test_a_generous_contact_applies_the_commanded_input(pkg, N):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B = B9
+    p = sm.SrbdParams()
+    xs, us, x = start(sm, p, B, N, 910 + N)  # fz in [40, 110]: no foot pulls
+    plan = feet_plan(sm, p, B, N, 911)  # fz_max >= 50: both feet in contact
+    wrench = np.random.default_rng(912).uniform(-20.0, 20.0, size=(B, 6))
+    generous = sm.SrbdContact(mu=1e6, Lt=(1e6, 1e6, 1e6), fz_hi=np.inf, fz_contact=5.0)
+    h = handle(capi, N, B, "none")
+    for use_plan in (True, False):
+        plan_t = device_plan(capi, plan) if use_plan else None
+        h.set_contact(None)
+        free = device_advance(capi, h, xs, us, x, plan_t, wrench, 3)
+        sat = np.zeros(B, dtype=np.uint32)
+        ct, st_t = device_contact(capi, generous, {"sat": sat})
+        h.set_contact(ct)
+        xs_t, us_t, x_t, u0 = device_advance(capi, h, xs, us, x, plan_t, wrench, 3)
+        assert torch.equal(u0, free[3]) and torch.equal(u0, _dev(us[:, 0])), use_plan
+        close(x_t, free[2].cpu().numpy(), use_plan)  # another instantiation: the tolerance, not bits
+        assert torch.equal(xs_t, free[0]) and torch.equal(us_t, free[1]), use_plan
+        assert not bool(st_t["sat"].any())
+
+
+# ---- 4. a robot that had fallen before the tick ----
+def test_a_robot_fallen_on_entry_is_frozen(pkg):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B, N, k = B9, 3, 6
+    p, xs, us, x, plan, plant, wrench, contact = advance_case(sm, N, 920)
+    plan_t = device_plan(capi, plan)
+    h = handle(capi, N, B, "none")
+    state = CH.zero_state(B)
+    state["alive"][:] = 5
+    state["sat"][:] = 0x100
+    ct, standing = device_contact(capi, contact, state)
+    h.set_contact(ct)
+    a = device_advance(capi, h, xs, us, x, plan_t, wrench, 3)
+    state["fallen"][k] = 1
+    ct, st_t = device_contact(capi, contact, state)
+    h.set_contact(ct)
+    b = device_advance(capi, h, xs, us, x, plan_t, wrench, 3)
+    got, was = state_of(st_t), state_of(standing)
+    assert torch.equal(b[2][k], _dev(x[k])) and not bool(b[3][k].any())  # x's bits, nothing applied
+    assert got["fallen"][k] == 1 and got["alive"][k] == 5 and got["sat"][k] == 0x100
+    assert was["fallen"][k] == 0 and was["alive"][k] == 6 and not torch.equal(a[2][k], _dev(x[k]))
+    # the shift is the plain shift: the bits of the run in which the robot stood
+    assert torch.equal(b[0], a[0]) and torch.equal(b[1], a[1])
+    assert torch.equal(b[0][:, :N], _dev(xs[:, 1:])) and torch.equal(b[1][:, :N - 1], _dev(us[:, 1:]))
+    others = [i for i in range(B) if i != k]
+    assert torch.equal(b[2][others], a[2][others]) and torch.equal(b[3][others], a[3][others])
+    for name in STATE:
+        assert np.array_equal(got[name][others], was[name][others]), name
+
+
+# ---- 5. non-finite inputs (NaN arithmetic only: every access is in bounds whatever the values) ----
+def test_a_non_finite_input_makes_the_robot_fall_and_keeps_its_state(pkg):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B, N = B9, 3
+    p, xs, us, x, plan, plant, wrench, contact = advance_case(sm, N, 930)
+    plan_t = device_plan(capi, plan)
+    h = handle(capi, N, B, "none")
+    ct, clean_st = device_contact(capi, contact, CH.zero_state(B))
+    h.set_contact(ct)
+    clean = device_advance(capi, h, xs, us, x, plan_t, wrench, 1)
+    bad = us.copy()
+    bad[6, 0, 4] = np.nan
+    bad[7, 0, 8] = np.inf
+    ct, st_t = device_contact(capi, contact, CH.zero_state(B))
+    h.set_contact(ct)
+    got = device_advance(capi, h, xs, bad, x, plan_t, wrench, 1)
+    st, was = state_of(st_t), state_of(clean_st)
+    for i in (6, 7):
+        assert was["fallen"][i] == 0 and st["fallen"][i] == 1 and st["alive"][i] == 0 and st["sat"][i] == 0
+        assert torch.equal(got[2][i], _dev(x[i])) and not bool(got[3][i].any())
+    others = [i for i in range(B) if i not in (6, 7)]
+    for u, v in zip(got, clean):
+        assert torch.equal(u[others], v[others])
+    for name in STATE:
+        assert np.array_equal(st[name][others], was[name][others]), name
+    same_state(st, host_advance(sm, p, xs, bad, x, plan, None, wrench, contact, 1, CH.zero_state(B))[2], "host")
+
+
+# ---- 6. the rollout with a contact ----
+# Chosen on the CPU (the asserts below hold them): with ROLL_SEED the host loop's smallest
+# comparison margin is >= 1e-6 (seeds 30..45 were tried; 39 has the largest, 5e-6); with
+# ROLL_Z_MIN robot 4 is below the threshold after the first tick, robot 3 sinks through it at the
+# second and the others stay above, every height at least 4e-5 away from it.
+ROLL_SEED = 39
+ROLL_Z_MIN = 1.0032
+ROLL_MU = 0.05    # ice: the friction clamp is active
+
+
+def rollout_case(sm, seed=ROLL_SEED):
+    B, N, T = 5, 5, 3
+    p = sm.SrbdParams()
+    xs, us, x, alpha, plan = RH.walking_case(sm, p, B, N, T, seed)
+    contact = sm.SrbdContact(mu=ROLL_MU, Lt=(0.0, 0.05, 0.05), fz_hi=400.0, fz_contact=5.0, z_min=ROLL_Z_MIN,
+                             cos_tilt_min=0.5)
+    return B, N, T, p, xs, us, x, alpha, plan, contact
+
+
+def test_rollout_with_a_contact(pkg, oracle):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B, N, T, p, xs, us, x, alpha, plan, contact = rollout_case(sm)
+    host = CH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, contact, alpha_reset=1.0)
+    assert host["margin"] >= 1e-6, host["margin"]
+    standing = np.ones(B, dtype=bool)
+    for t in range(T):  # the robots tested at tick t are those that stood before it
+        above, r33 = host["values"][t]
+        assert np.abs(above - contact.z_min)[standing].min() >= FALL_MARGIN, (t, above)
+        assert np.abs(r33 - contact.cos_tilt_min)[standing].min() >= FALL_MARGIN, (t, r33)
+        standing = host["fallen_log"][:, t] == 0
+    first = np.where(host["fallen_log"].any(axis=1), host["fallen_log"].argmax(axis=1), T)
+    assert len(set(first.tolist())) >= 2, first  # some robot falls, some robot survives
+    h = handle(capi, N, B, "none")
+    plan_t = device_plan(capi, plan)
+    ct, st_a = device_contact(capi, contact, CH.zero_state(B))
+    h.set_contact(ct)
+    a = [_dev(v) for v in (xs, us, x, alpha)]
+    logs_a = capi.srbd_rollout(h, *a, T, "none", NMPC, SQP_MAX_LOOP, plan=plan_t, alpha_reset=1.0)
+    ct, st_b = device_contact(capi, contact, CH.zero_state(B))
+    h.set_contact(ct)
+    b = [_dev(v) for v in (xs, us, x, alpha)]
+    logs_b = caller_loop(capi, h, B, N, T, "none", *b, plan_t, None, 1, 1.0)
+    names = ("xs", "us", "x", "alpha", "x_log", "u_log", "sqp_iter_log", "converged_log")
+    for name, u, v in zip(names, a + list(logs_a), b + list(logs_b)):
+        assert bool(torch.isfinite(u.double()).all()), name
+        assert torch.equal(u, v), name
+    got = state_of(st_a)
+    same_state(got, state_of(st_b), "caller's loop")
+    # against the host closed loop, at the closed-loop tolerances of tests/test_gpu_rollout.py
+    same_state(got, host["state"], "host")
+    assert got["sat"].any() and np.array_equal(got["alive"], first)
+    x_log, u_log = logs_a[0].cpu().numpy(), logs_a[1].cpu().numpy()
+    assert np.array_equal(logs_a[2].cpu().numpy(), host["sqp_iter"])
+    assert np.array_equal(logs_a[3].cpu().numpy(), host["converged"])
+    dt_x, dt_u = D_T[("none", 1.0)]
+    for t in range(1, T + 1):
+        print(f"tick {t}: max |x_log - host| {np.abs(x_log[:, t] - host['x_log'][:, t]).max():.3e}, "
+              f"max |u_log - host| {np.abs(u_log[:, t - 1] - host['u_log'][:, t - 1]).max():.3e}")
+    for t in range(1, T + 1):
+        ax = STEP_ATOL_X if t == 1 else max(STEP_ATOL_X, 10.0 * dt_x[t - 1])
+        au = STEP_ATOL_U if t == 1 else max(STEP_ATOL_U, 10.0 * dt_u[t - 1])
+        np.testing.assert_allclose(x_log[:, t], host["x_log"][:, t], rtol=1e-7, atol=ax, err_msg=f"x {t}")
+        np.testing.assert_allclose(u_log[:, t - 1], host["u_log"][:, t - 1], rtol=1e-7, atol=au, err_msg=f"u {t}")
+    # a fallen robot's x stays where it fell, and nothing is applied to it afterwards
+    for i in range(B):
+        for t in range(int(first[i]) + 1, T):
+            assert np.array_equal(x_log[i, t + 1], x_log[i, t]) and not u_log[i, t].any(), (i, t)
+
+
+# ---- 7. the replanning rollout: the planner's map is not the ground the feet stand on ----
+def test_gait_rollout_with_a_true_ground_is_the_callers_loop_bit_for_bit(pkg):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B, N, T, tick0 = 5, 5, 3, 10**12 + 3
+    p = sm.SrbdParams()
+    h = handle(capi, N, B, "none")
+    xs, us, x, alpha, gait, cmd, ref_pose, foot_now = TH.stairs_case(sm, p, B, N, T, 41)
+    believed = TH.stairs_terrain(sm, search=1)
+    s = TH.STAIRS  # the true ground: the stairs the planner believes in plus a perception error per robot
+    maps = np.stack([believed.height + TH.rough(s["ny"], s["nx"], 50 + m, 0.02) for m in range(2)])
+    truth = sm.SrbdTerrain(height=maps, x0=s["x0"], y0=s["y0"], cell=s["cell"], map_r=np.arange(B) % 2)
+    contact = sm.SrbdContact(mu=0.3, Lt=(0.0, 0.05, 0.05), fz_hi=400.0, fz_contact=0.5 * (gait.fz_swing + gait.fz_stance),
+                             ground_z=gait.ground_z, ground=truth, z_min=0.3, cos_tilt_min=0.5)
+    h.set_terrain(device_terrain(capi, believed))
+    gait_t, cmd_t = device_gait(capi, gait), _dev(cmd)
+    wrench_t = _dev(np.zeros((B, T, 6)))
+    runs = []
+    for loop in (False, True, False):  # the rollout, the caller's loop, the rollout on flat true ground
+        c = dataclasses.replace(contact, ground=None) if len(runs) == 2 else contact
+        ct, st = device_contact(capi, c, CH.zero_state(B))
+        h.set_contact(ct)
+        v = [_dev(w) for w in (xs, us, x, alpha, ref_pose, foot_now)]
+        if loop:
+            logs = gait_caller_loop(capi, h, gait_t, B, N, T, tick0, "none", cmd_t, *v, wrench_t, 1, 0.0)
+        else:
+            logs = capi.srbd_rollout_gait(h, gait_t, cmd_t, *v, T, tick0, "none", NMPC, SQP_MAX_LOOP, wrench=wrench_t)
+        runs.append((v + list(logs), state_of(st)))
+    names = ("xs", "us", "x", "alpha", "ref_pose", "foot_now", "x_log", "u_log", "sqp_iter_log", "converged_log",
+             "foot_log", "fz_log")
+    for name, u, v in zip(names, runs[0][0], runs[1][0]):
+        assert bool(torch.isfinite(u.double()).all()), name
+        assert torch.equal(u, v), name
+    same_state(runs[0][1], runs[1][1], "caller's loop")
+    assert int(runs[0][0][8].min()) >= 1  # the steps ran
+    assert runs[0][1]["sat"].any()  # swing feet and friction: limits were active
+    assert not torch.equal(runs[2][0][6], runs[0][0][6])  # and the true ground is felt
+
+
+# ---- 8. errors ----
+def test_contact_errors(pkg):
+    import torch
+    capi, sm = pkg.capi, pkg.srbd_model
+    B, N = 4, 3
+    h = handle(capi, N, B, "none")
+    inf, nan = float("inf"), float("nan")
+    H = _dev(TH.rough(5, 6, 1))
+    ints = lambda n=B: torch.zeros(n, dtype=torch.int32, device="cuda")
+    bad = [(dict(mu=-0.1), "mu"), (dict(mu=inf), "mu"), (dict(mu=nan), "mu"), (dict(Lt=(0.0, -1.0, 0.0)), "Lt"),
+           (dict(Lt=(nan, 0.0, 0.0)), "Lt"), (dict(Lt=(0.0, 0.0, inf)), "Lt"), (dict(fz_hi=0.0), "fz_hi"),
+           (dict(fz_hi=nan), "fz_hi"), (dict(fz_contact=-1.0), "fz_contact"), (dict(fz_contact=inf), "fz_contact"),
+           (dict(ground_z=nan), "ground_z"), (dict(z_min=inf), "z_min"), (dict(cos_tilt_min=1.5), "cos_tilt_min"),
+           (dict(cos_tilt_min=nan), "cos_tilt_min"),
+           (dict(ground=capi.Terrain(H, 0.0, 0.0, 0.0)), "cell"), (dict(ground=capi.Terrain(H, nan, 0.0, 0.1)), "x0"),
+           (dict(ground=capi.Terrain(torch.zeros(1, 6, dtype=torch.float64, device="cuda"), 0.0, 0.0, 0.1)), "nx and ny")]
+    for kw, word in bad:
+        with pytest.raises(capi.SrbdQpError, match=rf"\(-1\).*{word}"):
+            h.set_contact(capi.Contact(**kw))
+    # allowed: fz_hi = inf, a negative mu beside mu_r, a ground whose search / w_rough mean nothing
+    h.set_contact(capi.Contact(mu=-1.0, mu_r=_dev(np.full(B, 0.5)), fz_hi=inf,
+                               ground=capi.Terrain(H, 0.0, 0.0, 0.1, search=9, w_rough=-1.0)))
+    with pytest.raises(ValueError, match="alive needs"):
+        h.set_contact(capi.Contact(alive=ints()))
+    cs = capi.Contact().struct()
+    cs.alive = ints().data_ptr()
+    assert capi.lib().srbd_qp_srbd_set_contact_f64(h.ptr, cs) == -1  # the library's own check
+    with pytest.raises(capi.SrbdQpError, match=r"\(-2\)"):  # SRBD_QP_EDIM
+        capi.Handle(N, 4, 4, capacity=B).set_contact(capi.Contact())
+    with pytest.raises(ValueError, match="torch.int32"):
+        h.set_contact(capi.Contact(fallen=torch.zeros(B, dtype=torch.int64, device="cuda")))
+    h.set_contact(capi.Contact(fallen=ints(B - 1)))
+    p = sm.SrbdParams()
+    xs, us, x = start(sm, p, B, N, 1)
+    with pytest.raises(ValueError, match="3 rows"):
+        capi.srbd_advance(h, _dev(xs), _dev(us), x=_dev(x))
+    # a call without a plant state does not read the contact: the plain shift, the commanded input
+    fallen = ints()
+    h.set_contact(capi.Contact(mu=0.0, fallen=fallen))
+    xs_t, us_t = _dev(xs), _dev(us)
+    u0 = capi.srbd_advance(h, xs_t, us_t)
+    h.synchronize()
+    assert torch.equal(u0, _dev(us[:, 0])) and torch.equal(xs_t[:, :N], _dev(xs[:, 1:])) and not bool(fallen.any())
