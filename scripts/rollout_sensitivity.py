@@ -2,7 +2,8 @@
 """The inputs and the tolerance table of tests/test_gpu_rollout.py's comparison with the host
 closed loop, computed on the CPU.
 
-For each case (constraints, alpha_reset) of the test and a seed of rollout_host.walking_case:
+For each case (constraints, alpha_reset) of the test and a seed of rollout_host.walking_case,
+through rollout_host.closed_loop:
   * the conditions on the inputs: the host loop's smallest comparison margin over all ticks
     (wanted >= 1e-6) and the SQP iteration counts (wanted: at least two distinct);
   * d_t: the largest change of the host loop's x_log[t] / u_log[t-1] when the loop is rerun with
@@ -15,19 +16,19 @@ For each case (constraints, alpha_reset) of the test and a seed of rollout_host.
 
 With --robots the same for tests/test_gpu_robots.py's rollout: per-robot model
 parameters from robots_host.draw at seed + 100, the true robots from robots_host.draw_plant at
-seed + 200, two plant substeps, through robots_host.closed_loop; and how far the mismatch moves
-x_log (the same loop with plant = model).
+seed + 200, two plant substeps, through the same loop with model= and plant=; and how far the
+mismatch moves x_log (the same loop with plant = model).
 
     python scripts/rollout_sensitivity.py --robots --seed 30
 
 With --gait the same for tests/test_gpu_gait.py's replanning rollout: the inputs
-of gait_host.walking_case through gait_host.closed_loop, which plans every tick from the
+of gait_host.walking_case through the loop with gait=, which plans every tick from the
 measured state, so the perturbation of x reaches the later windows through the feedback.
 
     python scripts/rollout_sensitivity.py --gait --seed 30
 
 With --gait --terrain the same for tests/test_gpu_terrain.py's rollout up the stairs (DESIGN.md
-4.7f): terrain_host.stairs_case through terrain_host.closed_loop (search 1), with two more
+4.7f): terrain_host.stairs_case through the loop with gait= and terrain= (search 1), with two more
 conditions on the inputs: the smallest gap between the best and the second-best foothold cost
 over every touchdown of every tick (wanted >= 1e-6 cell^2), and the chosen candidates, which like
 the iteration counts must not change under the perturbation; the feet's d_t is printed too.
@@ -49,10 +50,8 @@ import helpers  # noqa: E402
 import robots_host as BH  # noqa: E402
 import rollout_host as RH  # noqa: E402
 import terrain_host as TH  # noqa: E402
+from srbd_device import NMPC  # noqa: E402
 
-NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
-            tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
-            split_step=1)
 CASES = [(c, a) for c in ("none", "box_u") for a in (0.0, 1.0)]
 B, N, T = 4, 10, 4
 
@@ -63,18 +62,15 @@ TERRAIN = None  # --gait --terrain: the SrbdTerrain; the inputs are terrain_host
 
 
 def run(sm, oracle, p, case, inputs):
+    xs, us, x, alpha = inputs[:4]
     if GAIT:
-        xs, us, x, alpha, gait, cmd, ref_pose, foot_now = inputs
-        if TERRAIN is not None:
-            return TH.closed_loop(sm, oracle, p, gait, TERRAIN, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC,
-                                  15, case[0], alpha_reset=case[1])
-        return GH.closed_loop(sm, oracle, p, gait, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, 15,
-                              case[0], alpha_reset=case[1])
-    xs, us, x, alpha, plan = inputs
-    if ROBOTS:
-        return BH.closed_loop(sm, oracle, ROBOTS[0], ROBOTS[1], plan, xs, us, x, alpha, T, NMPC, 15, case[0],
-                              substeps=2, alpha_reset=case[1])
-    return RH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, 15, case[0], alpha_reset=case[1])
+        gait, cmd, ref_pose, foot_now = inputs[4:]
+        features = dict(p=p, gait=gait, cmd=cmd, ref_pose=ref_pose, foot_now=foot_now, terrain=TERRAIN)
+    elif ROBOTS:
+        features = dict(model=ROBOTS[0], plant=ROBOTS[1], plan=inputs[4], substeps=2)
+    else:
+        features = dict(p=p, plan=inputs[4])
+    return RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, 15, case[0], alpha_reset=case[1], **features)
 
 
 def conditions(sm, oracle, p, seed):

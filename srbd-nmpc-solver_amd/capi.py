@@ -105,6 +105,23 @@ class LsParams(C.Structure):
                                          "beta_theta", "beta_alpha", "alpha_min")]
 
 
+def _check_tensor(name, t, dtypes, shape, device, holder="the trajectories", any_gpu=False, expected=None,
+                  or_else=""):
+    """ValueError unless t is a contiguous torch tensor of one of `dtypes`, of `shape`, on `device`.
+    shape: per dimension an int (that size), a str (a name such as "B": any size from 1) or None
+    (any size); `expected` replaces it in the message.  device: where `holder` lives; None: no
+    device is asked for, or with any_gpu any GPU is."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+        raise ValueError(f"{name} must be a {' or '.join(dict.fromkeys(str(d) for d in dtypes))} tensor{or_else}")
+    fits = lambda size, want: size == want if isinstance(want, int) else (want is None or size >= 1)
+    if t.dim() != len(shape) or not all(fits(s, w) for s, w in zip(t.shape, shape)):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {expected or tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if (any_gpu and t.device.type != "cuda") or (device is not None and t.device != device):
+        raise ValueError(f"{name} is on {t.device}, {holder} on {device if device is not None else 'a GPU'}")
+
 
 class PlanStruct(C.Structure):
     """srbd_plan_f64: device pointers, NULL = the value in srbd_model_params."""
@@ -137,15 +154,7 @@ class Plan:
             t = getattr(self, name)
             if t is None:
                 continue
-            want = (int(B), int(N) + extra, width)
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise ValueError(f"plan.{name} must be a torch.float64 tensor")
-            if tuple(t.shape) != want:
-                raise ValueError(f"plan.{name} has shape {tuple(t.shape)}, expected {want}")
-            if not t.is_contiguous():
-                raise ValueError(f"plan.{name} must be contiguous")
-            if device is not None and t.device != device:
-                raise ValueError(f"plan.{name} is on {t.device}, the trajectories on {device}")
+            _check_tensor(f"plan.{name}", t, (torch.float64,), (int(B), int(N) + extra, width), device)
             setattr(ps, name, t.data_ptr())
         return ps
 
@@ -193,18 +202,10 @@ class Robots:
                 continue
             if role == "plant" and name not in self.PLANT_FIELDS:
                 raise ValueError(f"robots.{name}: the plant role takes mass and Lbody only")
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise ValueError(f"robots.{name} must be a torch.float64 tensor")
-            if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < 1:
-                raise ValueError(f"robots.{name} has shape {tuple(t.shape)}, expected {('B',) + tail}")
+            _check_tensor(f"robots.{name}", t, (torch.float64,), ("B",) + tail, device, "the handle", any_gpu=True)
             if rows is not None and t.shape[0] != rows:
                 raise ValueError(f"robots.{name} has {t.shape[0]} rows, the other fields {rows}")
             rows = t.shape[0]
-            if not t.is_contiguous():
-                raise ValueError(f"robots.{name} must be contiguous")
-            if t.device.type != "cuda" or (device is not None and t.device != device):
-                raise ValueError(f"robots.{name} is on {t.device}, the handle on "
-                                 f"{device if device is not None else 'a GPU'}")
             setattr(rs, name, t.data_ptr())
         self.rows = rows
         return rs
@@ -234,29 +235,15 @@ class Terrain:
     def struct(self, device=None) -> TerrainStruct:
         import torch
         h = self.height
-        if not isinstance(h, torch.Tensor) or h.dtype != torch.float64:
-            raise ValueError("terrain.height must be a torch.float64 tensor")
-        if h.dim() not in (2, 3):
-            raise ValueError(f"terrain.height has shape {tuple(h.shape)}, expected [maps][ny][nx] or [ny][nx]")
-        if not h.is_contiguous():
-            raise ValueError("terrain.height must be contiguous")
-        if h.device.type != "cuda" or (device is not None and h.device != device):
-            raise ValueError(f"terrain.height is on {h.device}, the handle on "
-                             f"{device if device is not None else 'a GPU'}")
+        _check_tensor("terrain.height", h, (torch.float64,), (None,) * (3 if getattr(h, "ndim", 2) == 3 else 2), device,
+                      "the handle", any_gpu=True, expected="[maps][ny][nx] or [ny][nx]")
         maps = h.shape[0] if h.dim() == 3 else 1
         ts = TerrainStruct(h.data_ptr() or None, int(maps), int(h.shape[-1]), int(h.shape[-2]), float(self.x0),
                            float(self.y0), float(self.cell), None, int(self.search), float(self.w_rough))
         m = self.map_r
         self.rows = None
         if m is not None:
-            if not isinstance(m, torch.Tensor) or m.dtype != torch.int32:
-                raise ValueError("terrain.map_r must be a torch.int32 tensor")
-            if m.dim() != 1 or m.shape[0] < 1:
-                raise ValueError(f"terrain.map_r has shape {tuple(m.shape)}, expected (B,)")
-            if not m.is_contiguous():
-                raise ValueError("terrain.map_r must be contiguous")
-            if m.device != h.device:
-                raise ValueError(f"terrain.map_r is on {m.device}, the height on {h.device}")
+            _check_tensor("terrain.map_r", m, (torch.int32,), ("B",), h.device, "the height", expected="(B,)")
             ts.map_r = m.data_ptr()
             self.rows = int(m.shape[0])
         return ts
@@ -300,22 +287,13 @@ class Contact:
         cs.Ltx, cs.Lty, cs.Ltz = (float(v) for v in self.Lt)
         cs.ground_z, cs.z_min, cs.cos_tilt_min = float(self.ground_z), float(self.z_min), float(self.cos_tilt_min)
         rows = []
-        kinds = (("mu_r", (torch.float64,), "torch.float64"), ("fallen", (torch.int32,), "torch.int32"),
-                 ("alive", (torch.int32,), "torch.int32"),
-                 ("sat", (getattr(torch, "uint32", torch.int32), torch.int32), "torch.uint32 or torch.int32"))
-        for name, dtypes, text in kinds:
+        kinds = (("mu_r", (torch.float64,)), ("fallen", (torch.int32,)), ("alive", (torch.int32,)),
+                 ("sat", (getattr(torch, "uint32", torch.int32), torch.int32)))
+        for name, dtypes in kinds:
             t = getattr(self, name)
             if t is None:
                 continue
-            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
-                raise ValueError(f"contact.{name} must be a {text} tensor")
-            if t.dim() != 1 or t.shape[0] < 1:
-                raise ValueError(f"contact.{name} has shape {tuple(t.shape)}, expected (B,)")
-            if not t.is_contiguous():
-                raise ValueError(f"contact.{name} must be contiguous")
-            if t.device.type != "cuda" or (device is not None and t.device != device):
-                raise ValueError(f"contact.{name} is on {t.device}, the handle on "
-                                 f"{device if device is not None else 'a GPU'}")
+            _check_tensor(f"contact.{name}", t, dtypes, ("B",), device, "the handle", any_gpu=True, expected="(B,)")
             rows.append(int(t.shape[0]))
             setattr(cs, name, t.data_ptr())
         if self.alive is not None and self.fallen is None:
@@ -378,15 +356,7 @@ class Gait:
         for name, tail in self.INT_FIELDS.items():
             v = getattr(self, name)
             if isinstance(v, torch.Tensor):
-                want = (int(B),) + tail
-                if v.dtype != torch.int32:
-                    raise ValueError(f"gait.{name} must be a torch.int32 tensor or Python ints")
-                if tuple(v.shape) != want:
-                    raise ValueError(f"gait.{name} has shape {tuple(v.shape)}, expected {want}")
-                if not v.is_contiguous():
-                    raise ValueError(f"gait.{name} must be contiguous")
-                if device is not None and v.device != device:
-                    raise ValueError(f"gait.{name} is on {v.device}, the trajectories on {device}")
+                _check_tensor(f"gait.{name}", v, (torch.int32,), (int(B),) + tail, device, or_else=" or Python ints")
                 setattr(gs, name + "_r", v.data_ptr())
             elif tail:
                 if len(v) != 2:
@@ -403,6 +373,61 @@ class Gait:
         return gs
 
 
+def _prototypes():
+    """Every function include/srbd_qp.h declares: name -> (restype, argtypes, needed).  needed =
+    False marks a name that an older build, loaded through SRBD_QP_LIB for an A/B run, may lack:
+    lib() skips it there, and a call to it fails with AttributeError as it always did."""
+    P, i, vp = C.POINTER, C.c_int, C.c_void_p
+    h, st, mp, ls, plan = vp, P(Settings), P(ModelParams), P(LsParams), P(PlanStruct)
+    d64, s64, d32, s32 = P(Data), P(Solution), P(Data32), P(Solution32)
+    always, maybe = True, False
+    return {
+        "srbd_qp_abi_version": (i, [], always),
+        "srbd_qp_create": (i, [P(Dims), i, i, P(vp)], always),
+        "srbd_qp_destroy": (None, [h], always),
+        "srbd_qp_synchronize": (i, [h], always),
+        "srbd_qp_stream": (vp, [h], always),
+        "srbd_qp_workspace_bytes": (C.c_size_t, [h], always),
+        "srbd_qp_memory_bytes": (C.c_size_t, [h], maybe),  # ABI 9
+        "srbd_qp_default_settings": (None, [st], always),
+        "srbd_qp_check_settings": (i, [st], always),
+        "srbd_qp_status_string": (C.c_char_p, [i], always),
+        "srbd_qp_error_string": (C.c_char_p, [i], always),
+        "srbd_qp_last_error": (C.c_char_p, [], always),
+        "srbd_qp_solve_f64": (i, [h, i, st, d64, s64, vp], always),
+        "srbd_qp_solve_host_f64": (i, [h, i, st, d64, s64], always),
+        "srbd_qp_solve_f32": (i, [h, i, st, d32, s32, vp], always),
+        "srbd_qp_solve_host_f32": (i, [h, i, st, d32, s32], always),
+        "srbd_qp_solve_soft_f64": (i, [h, i, st, d64, P(Soft), s64, P(Slack), vp], maybe),  # soft boxes
+        "srbd_qp_solve_soft_host_f64": (i, [h, i, st, d64, P(Soft), s64, P(Slack)], maybe),
+        "srbd_qp_solve_host_cb_f64": (i, [h, i, st, d64, s64, FACTORS_CB, vp], maybe),  # ABI 12
+        "srbd_qp_host_staging_f64": (i, [h, i, st, d64, s64], maybe),  # ABI 10
+        "srbd_qp_multi_create": (i, [P(Dims), i, P(i), i, P(vp)], maybe),  # ABI 10
+        "srbd_qp_multi_destroy": (None, [vp], maybe),
+        "srbd_qp_multi_handle": (vp, [vp, i], maybe),
+        "srbd_qp_multi_solve_f64": (i, [vp, P(i), st, d64, s64, vp, vp, vp], maybe),
+        "srbd_qp_multi_solve_f32": (i, [vp, P(i), st, d32, s32, vp, vp, vp], maybe),  # ABI 11
+        "srbd_qp_srbd_default_params": (None, [mp], always),
+        "srbd_qp_srbd_default_linesearch": (None, [ls], always),
+        "srbd_qp_srbd_linearize_f64": (i, [h, i, mp, i, vp, vp, d64, vp], always),
+        "srbd_qp_srbd_linesearch_f64": (i, [h, i, mp, ls] + [vp] * 8, always),
+        "srbd_qp_srbd_nmpc_f64": (i, [h, i, mp, ls, st, i, i] + [vp] * 6, always),
+        "srbd_qp_srbd_linearize_plan_f64": (i, [h, i, mp, plan, i, vp, vp, d64, vp], maybe),  # plans
+        "srbd_qp_srbd_linesearch_plan_f64": (i, [h, i, mp, plan, ls] + [vp] * 8, maybe),
+        "srbd_qp_srbd_nmpc_plan_f64": (i, [h, i, mp, plan, ls, st, i, i] + [vp] * 6, maybe),
+        "srbd_qp_srbd_advance_f64": (i, [h, i, mp, plan, P(AdvanceStruct)] + [vp] * 5, maybe),  # the closed loop
+        "srbd_qp_srbd_rollout_f64": (i, [h, i, mp, plan, ls, st, i, i, P(RolloutStruct)] + [vp] * 4, maybe),
+        "srbd_qp_srbd_set_robots_f64": (i, [h, i, P(RobotsStruct)], maybe),
+        "srbd_qp_srbd_set_terrain_f64": (i, [h, P(TerrainStruct)], maybe),
+        "srbd_qp_srbd_terrain_height_f64": (i, [h, i] + [vp] * 4, maybe),
+        "srbd_qp_srbd_set_contact_f64": (i, [h, P(ContactStruct)], maybe),
+        "srbd_qp_srbd_gait_plan_f64": (i, [h, i, mp, P(GaitStruct), vp, vp, C.c_longlong] + [vp] * 7, maybe),
+        "srbd_qp_srbd_rollout_gait_f64": (i, [h, i, mp, P(GaitStruct), P(RolloutGaitStruct), ls, st, i, i,
+                                              P(RolloutStruct)] + [vp] * 4, maybe),
+    }
+
+
+PROTOTYPES = _prototypes()
 _lib = None
 
 
@@ -420,138 +445,10 @@ def lib():
         except ImportError:  # pragma: no cover - C-only consumers
             pass
         L = C.CDLL(str(LIB_PATH))
-        L.srbd_qp_create.argtypes = [C.POINTER(Dims), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.srbd_qp_create.restype = C.c_int
-        L.srbd_qp_solve_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings), C.POINTER(Data),
-                                        C.POINTER(Solution), C.c_void_p]
-        L.srbd_qp_solve_f64.restype = C.c_int
-        L.srbd_qp_solve_host_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
-                                             C.POINTER(Data), C.POINTER(Solution)]
-        L.srbd_qp_solve_host_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_solve_soft_f64"):  # soft boxes (older builds: A/B runs)
-            L.srbd_qp_solve_soft_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings), C.POINTER(Data),
-                                                 C.POINTER(Soft), C.POINTER(Solution), C.POINTER(Slack),
-                                                 C.c_void_p]
-            L.srbd_qp_solve_soft_f64.restype = C.c_int
-            L.srbd_qp_solve_soft_host_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
-                                                      C.POINTER(Data), C.POINTER(Soft), C.POINTER(Solution),
-                                                      C.POINTER(Slack)]
-            L.srbd_qp_solve_soft_host_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_solve_host_cb_f64"):  # ABI 12
-            L.srbd_qp_solve_host_cb_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings), C.POINTER(Data),
-                                                    C.POINTER(Solution), FACTORS_CB, C.c_void_p]
-            L.srbd_qp_solve_host_cb_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_multi_create"):  # ABI 10
-            L.srbd_qp_multi_create.argtypes = [C.POINTER(Dims), C.c_int, C.POINTER(C.c_int), C.c_int,
-                                               C.POINTER(C.c_void_p)]
-            L.srbd_qp_multi_create.restype = C.c_int
-            L.srbd_qp_multi_destroy.argtypes = [C.c_void_p]
-            L.srbd_qp_multi_destroy.restype = None
-            L.srbd_qp_multi_handle.argtypes = [C.c_void_p, C.c_int]
-            L.srbd_qp_multi_handle.restype = C.c_void_p
-            L.srbd_qp_multi_solve_f64.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Settings),
-                                                  C.POINTER(Data), C.POINTER(Solution), C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]
-            L.srbd_qp_multi_solve_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_multi_solve_f32"):  # ABI 11
-            L.srbd_qp_multi_solve_f32.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(Settings),
-                                                  C.POINTER(Data32), C.POINTER(Solution32), C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]
-            L.srbd_qp_multi_solve_f32.restype = C.c_int
-        if hasattr(L, "srbd_qp_host_staging_f64"):  # ABI 10 (older builds: A/B runs)
-            L.srbd_qp_host_staging_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
-                                                   C.POINTER(Data), C.POINTER(Solution)]
-            L.srbd_qp_host_staging_f64.restype = C.c_int
-        L.srbd_qp_solve_f32.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
-                                        C.POINTER(Data32), C.POINTER(Solution32), C.c_void_p]
-        L.srbd_qp_solve_f32.restype = C.c_int
-        L.srbd_qp_solve_host_f32.argtypes = [C.c_void_p, C.c_int, C.POINTER(Settings),
-                                             C.POINTER(Data32), C.POINTER(Solution32)]
-        L.srbd_qp_solve_host_f32.restype = C.c_int
-        L.srbd_qp_destroy.argtypes = [C.c_void_p]
-        L.srbd_qp_destroy.restype = None
-        L.srbd_qp_synchronize.argtypes = [C.c_void_p]
-        L.srbd_qp_synchronize.restype = C.c_int
-        L.srbd_qp_stream.argtypes = [C.c_void_p]
-        L.srbd_qp_stream.restype = C.c_void_p
-        L.srbd_qp_workspace_bytes.argtypes = [C.c_void_p]
-        L.srbd_qp_workspace_bytes.restype = C.c_size_t
-        try:  # ABI >= 9 (older builds are still loaded by A/B scripts)
-            L.srbd_qp_memory_bytes.argtypes = [C.c_void_p]
-            L.srbd_qp_memory_bytes.restype = C.c_size_t
-        except AttributeError:
-            pass
-        L.srbd_qp_default_settings.argtypes = [C.POINTER(Settings)]
-        L.srbd_qp_default_settings.restype = None
-        L.srbd_qp_check_settings.argtypes = [C.POINTER(Settings)]
-        L.srbd_qp_check_settings.restype = C.c_int
-        L.srbd_qp_status_string.argtypes = [C.c_int]
-        L.srbd_qp_status_string.restype = C.c_char_p
-        L.srbd_qp_error_string.argtypes = [C.c_int]
-        L.srbd_qp_error_string.restype = C.c_char_p
-        L.srbd_qp_last_error.argtypes = []
-        L.srbd_qp_last_error.restype = C.c_char_p
-        L.srbd_qp_srbd_default_params.argtypes = [C.POINTER(ModelParams)]
-        L.srbd_qp_srbd_default_params.restype = None
-        L.srbd_qp_srbd_linearize_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams), C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.POINTER(Data), C.c_void_p]
-        L.srbd_qp_srbd_linearize_f64.restype = C.c_int
-        L.srbd_qp_srbd_default_linesearch.argtypes = [C.POINTER(LsParams)]
-        L.srbd_qp_srbd_default_linesearch.restype = None
-        L.srbd_qp_srbd_linesearch_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                  C.POINTER(LsParams)] + [C.c_void_p] * 8
-        L.srbd_qp_srbd_linesearch_f64.restype = C.c_int
-        L.srbd_qp_srbd_nmpc_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                            C.POINTER(LsParams), C.POINTER(Settings), C.c_int,
-                                            C.c_int] + [C.c_void_p] * 6
-        L.srbd_qp_srbd_nmpc_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_srbd_nmpc_plan_f64"):  # plans (older builds: A/B runs)
-            L.srbd_qp_srbd_linearize_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                          C.POINTER(PlanStruct), C.c_int, C.c_void_p,
-                                                          C.c_void_p, C.POINTER(Data), C.c_void_p]
-            L.srbd_qp_srbd_linearize_plan_f64.restype = C.c_int
-            L.srbd_qp_srbd_linesearch_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                           C.POINTER(PlanStruct),
-                                                           C.POINTER(LsParams)] + [C.c_void_p] * 8
-            L.srbd_qp_srbd_linesearch_plan_f64.restype = C.c_int
-            L.srbd_qp_srbd_nmpc_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                     C.POINTER(PlanStruct), C.POINTER(LsParams),
-                                                     C.POINTER(Settings), C.c_int,
-                                                     C.c_int] + [C.c_void_p] * 6
-            L.srbd_qp_srbd_nmpc_plan_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_srbd_rollout_f64"):  # the closed loop (older builds: A/B runs)
-            L.srbd_qp_srbd_advance_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                   C.POINTER(PlanStruct),
-                                                   C.POINTER(AdvanceStruct)] + [C.c_void_p] * 5
-            L.srbd_qp_srbd_advance_f64.restype = C.c_int
-            L.srbd_qp_srbd_rollout_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                   C.POINTER(PlanStruct), C.POINTER(LsParams),
-                                                   C.POINTER(Settings), C.c_int, C.c_int,
-                                                   C.POINTER(RolloutStruct)] + [C.c_void_p] * 4
-            L.srbd_qp_srbd_rollout_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_srbd_set_robots_f64"):  # robots (older builds: A/B runs)
-            L.srbd_qp_srbd_set_robots_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(RobotsStruct)]
-            L.srbd_qp_srbd_set_robots_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_srbd_set_terrain_f64"):  # terrain (older builds: A/B runs)
-            L.srbd_qp_srbd_set_terrain_f64.argtypes = [C.c_void_p, C.POINTER(TerrainStruct)]
-            L.srbd_qp_srbd_set_terrain_f64.restype = C.c_int
-            L.srbd_qp_srbd_terrain_height_f64.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
-            L.srbd_qp_srbd_terrain_height_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_srbd_set_contact_f64"):  # the contact model (older builds: A/B runs)
-            L.srbd_qp_srbd_set_contact_f64.argtypes = [C.c_void_p, C.POINTER(ContactStruct)]
-            L.srbd_qp_srbd_set_contact_f64.restype = C.c_int
-        if hasattr(L, "srbd_qp_srbd_gait_plan_f64"):  # the gait planner (older builds: A/B runs)
-            L.srbd_qp_srbd_gait_plan_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                     C.POINTER(GaitStruct), C.c_void_p, C.c_void_p,
-                                                     C.c_longlong] + [C.c_void_p] * 7
-            L.srbd_qp_srbd_gait_plan_f64.restype = C.c_int
-            L.srbd_qp_srbd_rollout_gait_f64.argtypes = [C.c_void_p, C.c_int, C.POINTER(ModelParams),
-                                                        C.POINTER(GaitStruct), C.POINTER(RolloutGaitStruct),
-                                                        C.POINTER(LsParams), C.POINTER(Settings), C.c_int,
-                                                        C.c_int, C.POINTER(RolloutStruct)] + [C.c_void_p] * 4
-            L.srbd_qp_srbd_rollout_gait_f64.restype = C.c_int
-        L.srbd_qp_abi_version.argtypes = []
-        L.srbd_qp_abi_version.restype = C.c_int
+        for name, (restype, argtypes, needed) in PROTOTYPES.items():
+            if needed or hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -888,38 +785,26 @@ def model_params(p) -> ModelParams:
     return m
 
 
-def _check_robots(handle, B) -> None:
-    """The handle's robots (Handle.set_robots) are read at rows 0..B-1: ValueError if one has fewer."""
-    for r in getattr(handle, "_robots", ()):
-        if r is not None and r.rows is not None and r.rows < int(B):
-            raise ValueError(f"the handle's robots have {r.rows} rows, the batch {int(B)}")
+_TOO_FEW_ROWS = {"robots": "the handle's robots have {} rows", "terrain": "the handle's terrain has a map_r of {} rows",
+                 "contact": "the handle's contact has tensors of {} rows"}
 
 
-def _check_terrain(handle, B) -> None:
-    """The handle's terrain (Handle.set_terrain) reads map_r at rows 0..B-1: ValueError if it has fewer."""
-    t = getattr(handle, "_terrain", None)
-    if t is not None and t.rows is not None and t.rows < int(B):
-        raise ValueError(f"the handle's terrain has a map_r of {t.rows} rows, the batch {int(B)}")
+def _check_rows(handle, B, *holders) -> None:
+    """The call reads (a contact: also writes) rows 0..B-1 of what the handle holds from
+    Handle.set_robots / set_terrain / set_contact, those named in `holders`: ValueError if one has
+    fewer rows."""
+    for kind in holders:
+        held = getattr(handle, "_" + kind, None)
+        for one in held if isinstance(held, tuple) else (held,):
+            if one is not None and one.rows is not None and one.rows < int(B):
+                raise ValueError(_TOO_FEW_ROWS[kind].format(one.rows) + f", the batch {int(B)}")
 
 
-def _check_contact(handle, B) -> None:
-    """The handle's contact (Handle.set_contact) is read and written at rows 0..B-1: ValueError if
-    one of its tensors has fewer."""
-    c = getattr(handle, "_contact", None)
-    if c is not None and c.rows is not None and c.rows < int(B):
-        raise ValueError(f"the handle's contact has tensors of {c.rows} rows, the batch {int(B)}")
-
-
-def _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream):
-    """srbd_qp_srbd_linearize_f64, or the _plan_ entry point when a plan is given."""
-    tail = (SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()), C.c_void_p(us.data_ptr()),
-            C.byref(data), C.c_void_p(stream or None))
-    if plan_ref is None:
-        check(lib().srbd_qp_srbd_linearize_f64(handle.ptr, int(B), C.byref(p), *tail),
-              "srbd_qp_srbd_linearize_f64")
-    else:
-        check(lib().srbd_qp_srbd_linearize_plan_f64(handle.ptr, int(B), C.byref(p), plan_ref, *tail),
-              "srbd_qp_srbd_linearize_plan_f64")
+def _call_with_plan(stem, handle, B, p, plan_ref, *tail) -> None:
+    """srbd_qp_srbd_<stem>_f64, or its _plan_ twin when a plan is given."""
+    name = f"srbd_qp_srbd_{stem}_f64" if plan_ref is None else f"srbd_qp_srbd_{stem}_plan_f64"
+    head = (handle.ptr, int(B), C.byref(p)) + (() if plan_ref is None else (plan_ref,))
+    check(getattr(lib(), name)(*head, *tail), name)
 
 
 def srbd_linearize(handle: Handle, xs, us, constraints: str = "none",
@@ -930,38 +815,28 @@ def srbd_linearize(handle: Handle, xs, us, constraints: str = "none",
     Asynchronous on the handle's stream: keep xs / us alive (and do not reuse
     their memory from another stream) until that stream has finished.
     `plan` (a Plan) overrides the reference, the feet and the force limits per robot and
-    stage; its tensors must stay alive like xs / us.
+    stage; its tensors must stay alive like xs / us.  `out`: the dict a previous call returned,
+    to write into (no allocation).
     Returns (dict of device tensors in the C-ABI layout, Data)."""
     import torch
     B, N1, _ = xs.shape
     N = N1 - 1
-    dev = xs.device
-    plan_ref = _plan_ref(plan, B, N, dev)
-    _check_robots(handle, B)
-    f = dict(dtype=torch.float64, device=dev)
-    if out is not None:  # caller-owned buffers from a previous call (no allocation)
-        t = out
-        data = Data(**{k: _tensor_ptr(t.get(k)) or None for k in DATA_FIELDS})
-        p = params or default_model_params()
-        o = _order_before(handle, stream, True)
-        _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream)
-        _order_after(o)
-        return t, data
-    t = {"A": torch.empty(B, N, 144, **f), "B": torch.empty(B, N, 144, **f),
-         "b": torch.empty(B, N, 12, **f), "Q": torch.empty(B, N + 1, 144, **f),
-         "S": torch.empty(B, N, 144, **f), "R": torch.empty(B, N, 144, **f),
-         "q": torch.empty(B, N + 1, 12, **f), "r": torch.empty(B, N, 12, **f)}
-    if constraints == "box_u":
-        t["lbu"] = torch.empty(B, N, 12, **f)
-        t["ubu"] = torch.empty(B, N, 12, **f)
-    elif constraints == "cone":
-        t["D"] = torch.empty(B, N, 24 * 12, **f)
-        for k in ("lg", "ug", "lg_mask", "ug_mask"):
-            t[k] = torch.empty(B, N + 1, 24, **f)
+    plan_ref = _plan_ref(plan, B, N, xs.device)
+    _check_rows(handle, B, "robots")
+    t = out
+    if t is None:
+        rows = {"A": (N, 144), "B": (N, 144), "b": (N, 12), "Q": (N + 1, 144), "S": (N, 144), "R": (N, 144),
+                "q": (N + 1, 12), "r": (N, 12)}
+        if constraints == "box_u":
+            rows.update(lbu=(N, 12), ubu=(N, 12))
+        elif constraints == "cone":
+            rows.update(D=(N, 24 * 12), lg=(N + 1, 24), ug=(N + 1, 24), lg_mask=(N + 1, 24), ug_mask=(N + 1, 24))
+        t = {k: torch.empty(B, *shape, dtype=torch.float64, device=xs.device) for k, shape in rows.items()}
     data = Data(**{k: _tensor_ptr(t.get(k)) or None for k in DATA_FIELDS})
     p = params or default_model_params()
     o = _order_before(handle, stream, True)
-    _linearize_call(handle, B, p, plan_ref, constraints, xs, us, data, stream)
+    _call_with_plan("linearize", handle, B, p, plan_ref, SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()),
+                    C.c_void_p(us.data_ptr()), C.byref(data), C.c_void_p(stream or None))
     _order_after(o)
     return t, data
 
@@ -981,21 +856,15 @@ def srbd_linesearch(handle: Handle, xs, us, dx, du, alpha, params: Optional[Mode
     import torch
     B = xs.shape[0]
     plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
-    _check_robots(handle, B)
+    _check_rows(handle, B, "robots")
     merit = torch.empty(B, 3, dtype=torch.float64, device=xs.device)
     conv = torch.empty(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
     lp = ls or default_linesearch()
     ptr = lambda t: C.c_void_p(t.data_ptr())
     o = _order_before(handle, stream, True)
-    tail = (C.byref(lp), ptr(xs), ptr(us), ptr(dx), ptr(du), ptr(alpha), ptr(merit), ptr(conv),
-            C.c_void_p(stream or None))
-    if plan_ref is None:
-        check(lib().srbd_qp_srbd_linesearch_f64(handle.ptr, int(B), C.byref(p), *tail),
-              "srbd_qp_srbd_linesearch_f64")
-    else:
-        check(lib().srbd_qp_srbd_linesearch_plan_f64(handle.ptr, int(B), C.byref(p), plan_ref, *tail),
-              "srbd_qp_srbd_linesearch_plan_f64")
+    _call_with_plan("linesearch", handle, B, p, plan_ref, C.byref(lp), ptr(xs), ptr(us), ptr(dx), ptr(du),
+                    ptr(alpha), ptr(merit), ptr(conv), C.c_void_p(stream or None))
     _order_after(o)
     return merit, conv
 
@@ -1013,7 +882,7 @@ def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
     import torch
     B = xs.shape[0]
     plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
-    _check_robots(handle, B)
+    _check_rows(handle, B, "robots")
     it = torch.zeros(B, dtype=torch.int32, device=xs.device)
     conv = torch.zeros(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
@@ -1021,27 +890,15 @@ def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
     s = settings_struct(settings)
     ptr = lambda t: C.c_void_p(t.data_ptr())
     o = _order_before(handle, 0, True)
-    tail = (C.byref(lp), C.byref(s), SRBD_CONSTRAINTS[constraints], int(sqp_max_loop), ptr(xs),
-            ptr(us), ptr(x0), ptr(alpha), ptr(it), ptr(conv))
-    if plan_ref is None:
-        check(lib().srbd_qp_srbd_nmpc_f64(handle.ptr, int(B), C.byref(p), *tail), "srbd_qp_srbd_nmpc_f64")
-    else:
-        check(lib().srbd_qp_srbd_nmpc_plan_f64(handle.ptr, int(B), C.byref(p), plan_ref, *tail),
-              "srbd_qp_srbd_nmpc_plan_f64")
+    _call_with_plan("nmpc", handle, B, p, plan_ref, C.byref(lp), C.byref(s), SRBD_CONSTRAINTS[constraints],
+                    int(sqp_max_loop), ptr(xs), ptr(us), ptr(x0), ptr(alpha), ptr(it), ptr(conv))
     _order_after(o)
     return it, conv
 
 
 def _check_f64(name, t, shape, device):
     import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-        raise ValueError(f"{name} must be a torch.float64 tensor")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    if t.device != device:
-        raise ValueError(f"{name} is on {t.device}, the trajectories on {device}")
+    _check_tensor(name, t, (torch.float64,), tuple(int(n) for n in shape), device)
 
 
 def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wrench=None,
@@ -1064,8 +921,7 @@ def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wr
     if wrench is not None:
         _check_f64("wrench", wrench, (B, 6), dev)
     plan_ref = _plan_ref(plan, B, N, dev)
-    _check_robots(handle, B)
-    _check_contact(handle, B)
+    _check_rows(handle, B, "robots", "contact")
     u0 = torch.empty(B, 12, dtype=torch.float64, device=dev)
     adv = AdvanceStruct(int(substeps), _tensor_ptr(wrench) or None)
     p = params or default_model_params()
@@ -1076,6 +932,21 @@ def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wr
           "srbd_qp_srbd_advance_f64")
     _order_after(o)
     return u0
+
+
+def _rollout_logs(B, T, plan_stages, dev, wrench, substeps, alpha_reset):
+    """((x_log, u_log, sqp_iter_log, converged_log) of a rollout of T ticks, zeroed; the
+    RolloutStruct that points at them)."""
+    import torch
+    rows = max(T, 0)
+    x_log = torch.zeros(B, rows + 1, 12, dtype=torch.float64, device=dev)
+    u_log = torch.zeros(B, rows, 12, dtype=torch.float64, device=dev)
+    it_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
+    cv_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
+    roll = RolloutStruct(T, int(plan_stages), int(substeps), _tensor_ptr(wrench) or None, float(alpha_reset),
+                         x_log.data_ptr(), u_log.data_ptr() or None, it_log.data_ptr() or None,
+                         cv_log.data_ptr() or None)
+    return (x_log, u_log, it_log, cv_log), roll
 
 
 def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str = "none",
@@ -1092,7 +963,6 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
     alpha_reset > 0 starts every tick's line search from that alpha; 0 keeps the reference's
     persistent alpha_.  Synchronous.  Returns (x_log [B][ticks+1][12], u_log [B][ticks][12],
     sqp_iter_log [B][ticks], converged_log [B][ticks]) device tensors."""
-    import torch
     B, N, T = us.shape[0], us.shape[1], int(ticks)
     dev = xs.device
     _check_f64("xs", xs, (B, N + 1, 12), dev)
@@ -1103,16 +973,8 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
         _check_f64("wrench", wrench, (B, max(T, 0), 6), dev)
     P = N + T - 1 if plan_stages is None else int(plan_stages)
     plan_ref = _plan_ref(plan, B, P, dev)
-    _check_robots(handle, B)
-    _check_contact(handle, B)
-    rows = max(T, 0)
-    x_log = torch.zeros(B, rows + 1, 12, dtype=torch.float64, device=dev)
-    u_log = torch.zeros(B, rows, 12, dtype=torch.float64, device=dev)
-    it_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
-    cv_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
-    roll = RolloutStruct(T, P, int(substeps), _tensor_ptr(wrench) or None, float(alpha_reset),
-                         x_log.data_ptr(), u_log.data_ptr() or None, it_log.data_ptr() or None,
-                         cv_log.data_ptr() or None)
+    _check_rows(handle, B, "robots", "contact")
+    logs, roll = _rollout_logs(B, T, P, dev, wrench, substeps, alpha_reset)
     p = params or default_model_params()
     lp = ls or default_linesearch()
     s = settings_struct(settings)
@@ -1123,7 +985,7 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
                                          ptr(xs), ptr(us), ptr(x), ptr(alpha)),
           "srbd_qp_srbd_rollout_f64")
     _order_after(o)
-    return x_log, u_log, it_log, cv_log
+    return logs
 
 
 def _check_gait_state(B, dev, x, ref_pose, foot_now):
@@ -1157,8 +1019,7 @@ def srbd_gait_plan(handle: Handle, gait: Gait, cmd, x, tick: int, ref_pose, foot
     elif None in (out.x_ref, out.foot_r, out.foot_l, out.fz_max):
         raise ValueError("out needs all four of x_ref, foot_r, foot_l, fz_max")
     out.struct(B, N, dev)  # the shapes
-    _check_robots(handle, B)
-    _check_terrain(handle, B)
+    _check_rows(handle, B, "robots", "terrain")
     p = params or default_model_params()
     ptr = lambda t: C.c_void_p(t.data_ptr())
     o = _order_before(handle, stream, True)
@@ -1193,19 +1054,10 @@ def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pos
     if wrench is not None:
         _check_f64("wrench", wrench, (B, rows, 6), dev)
     gs = gait.struct(B, dev)
-    _check_robots(handle, B)
-    _check_terrain(handle, B)
-    _check_contact(handle, B)
-    f = dict(dtype=torch.float64, device=dev)
-    x_log = torch.zeros(B, rows + 1, 12, **f)
-    u_log = torch.zeros(B, rows, 12, **f)
-    it_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
-    cv_log = torch.zeros(B, rows, dtype=torch.int32, device=dev)
-    foot_log = torch.zeros(B, rows, 2, 3, **f)
-    fz_log = torch.zeros(B, rows, 2, **f)
-    roll = RolloutStruct(T, 0, int(substeps), _tensor_ptr(wrench) or None, float(alpha_reset),
-                         x_log.data_ptr(), u_log.data_ptr() or None, it_log.data_ptr() or None,
-                         cv_log.data_ptr() or None)
+    _check_rows(handle, B, "robots", "terrain", "contact")
+    logs, roll = _rollout_logs(B, T, 0, dev, wrench, substeps, alpha_reset)
+    foot_log = torch.zeros(B, rows, 2, 3, dtype=torch.float64, device=dev)
+    fz_log = torch.zeros(B, rows, 2, dtype=torch.float64, device=dev)
     gio = RolloutGaitStruct(cmd.data_ptr() or None, ref_pose.data_ptr(), foot_now.data_ptr(), int(tick0),
                             foot_log.data_ptr() or None, fz_log.data_ptr() or None)
     p = params or default_model_params()
@@ -1218,7 +1070,7 @@ def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pos
                                               int(sqp_max_loop), C.byref(roll), ptr(xs), ptr(us), ptr(x),
                                               ptr(alpha)), "srbd_qp_srbd_rollout_gait_f64")
     _order_after(o)
-    return x_log, u_log, it_log, cv_log, foot_log, fz_log
+    return logs + (foot_log, fz_log)
 
 
 def srbd_terrain_height(handle: Handle, xy, map=None, stream: int = 0):
@@ -1232,9 +1084,7 @@ def srbd_terrain_height(handle: Handle, xy, map=None, stream: int = 0):
     n, dev = xy.shape[0], xy.device
     _check_f64("xy", xy, (n, 2), dev)
     if map is not None:
-        if not isinstance(map, torch.Tensor) or map.dtype != torch.int32 or tuple(map.shape) != (n,) \
-                or not map.is_contiguous() or map.device != dev:
-            raise ValueError(f"map must be a contiguous torch.int32 tensor of shape ({n},) on {dev}")
+        _check_tensor("map", map, (torch.int32,), (int(n),), dev, "xy")
     out = torch.empty(n, dtype=torch.float64, device=dev)
     o = _order_before(handle, stream, True)
     check(lib().srbd_qp_srbd_terrain_height_f64(handle.ptr, int(n), C.c_void_p(xy.data_ptr() or None),

@@ -1,58 +1,18 @@
-"""TEST INFRASTRUCTURE ONLY -- the host closed loop the replanning device rollout
-(srbd_qp_srbd_rollout_gait_f64) is compared against: per tick srbd_model.gait_plan from the
-measured state, then the host SQP loop of tests/nmpc_plan_host.py on that window, then
-srbd_model.plant_step and srbd_model.shift_guess, in the order include/srbd_qp.h states."""
+"""TEST INFRASTRUCTURE ONLY -- the host side of the gait planner (srbd_qp_srbd_gait_plan_f64,
+srbd_qp_srbd_rollout_gait_f64): the gaits and inputs of the gait tests and the contact
+schedule's integers restated.  The host closed loop that replans every tick is
+tests/rollout_host.py's closed_loop(gait=...)."""
 from __future__ import annotations
 
 import numpy as np
 
-import nmpc_plan_host as PH
-
-__all__ = ["closed_loop", "walking_gait", "walking_case", "special_gaits", "schedule", "random_inputs"]
+__all__ = ["rot", "walking_gait", "walking_case", "special_gaits", "schedule", "random_inputs"]
 
 
-def closed_loop(sm, oracle, p, gait, cmd, xs, us, x, alpha, ref_pose, foot_now, ticks, settings,
-                sqp_max_loop, constraints="none", tick0=0, wrench=None, substeps=1, alpha_reset=0.0):
-    """`ticks` ticks from the guess xs [B][N+1][12], us [B][N][12], the plant state x [B][12],
-    alpha [B], ref_pose [B][3] and foot_now [B][2][3] under the gait and cmd [B][ticks][4].
-    Returns rollout_host.closed_loop's dict plus foot_log [B][ticks][2][3], fz_log [B][ticks][2],
-    ref_pose, foot_now and windows (each tick's SrbdPlan)."""
-    B, N = us.shape[0], us.shape[1]
-    xs, us, x = xs.copy(), us.copy(), x.copy()
-    alpha = np.array(alpha, dtype=np.float64)
-    ref_pose, foot_now = np.array(ref_pose, dtype=np.float64), np.array(foot_now, dtype=np.float64)
-    x_log = np.empty((B, ticks + 1, 12))
-    u_log = np.empty((B, ticks, 12))
-    it_log = np.zeros((B, ticks), dtype=np.int32)
-    cv_log = np.zeros((B, ticks), dtype=np.int32)
-    foot_log = np.empty((B, ticks, 2, 3))
-    fz_log = np.empty((B, ticks, 2))
-    x_log[:, 0] = x
-    margin, steps, windows = np.inf, [], []
-    for t in range(ticks):
-        w, ref_pose, foot_now = sm.gait_plan(p, gait, cmd[:, t], x, tick0 + t, ref_pose, foot_now, N)
-        windows.append(w)
-        if alpha_reset > 0.0:
-            alpha[:] = alpha_reset
-        res = [PH.sqp_loop(sm, oracle, p, w.robot(i), xs[i], us[i], x[i], float(alpha[i]), settings,
-                           sqp_max_loop, constraints) for i in range(B)]
-        steps.append(res)
-        xs = np.stack([r[0] for r in res])
-        us = np.stack([r[1] for r in res])
-        alpha = np.array([r[2] for r in res], dtype=np.float64)
-        it_log[:, t] = [r[3] for r in res]
-        cv_log[:, t] = [int(r[4]) for r in res]
-        margin = min([margin] + [r[5] for r in res])
-        foot_log[:, t, 0], foot_log[:, t, 1], fz_log[:, t] = w.foot_r[:, 0], w.foot_l[:, 0], w.fz_max[:, 0]
-        u0 = us[:, 0].copy()
-        x = sm.plant_step(x, u0, p, w.foot_r[:, 0], w.foot_l[:, 0], None if wrench is None else wrench[:, t],
-                          substeps)
-        xs, us = sm.shift_guess(xs, us, p, w)
-        u_log[:, t] = u0
-        x_log[:, t + 1] = x
-    return dict(x_log=x_log, u_log=u_log, sqp_iter=it_log, converged=cv_log, xs=xs, us=us, x=x, alpha=alpha,
-                margin=margin, steps=steps, foot_log=foot_log, fz_log=fz_log, ref_pose=ref_pose,
-                foot_now=foot_now, windows=windows)
+def rot(yaw, v):
+    """Rz(yaw) v for v [...][2]."""
+    c, s = np.cos(yaw), np.sin(yaw)
+    return np.stack([c * v[..., 0] - s * v[..., 1], s * v[..., 0] + c * v[..., 1]], axis=-1)
 
 
 def walking_gait(sm, p, B, k_raibert=0.03, anchor=0):

@@ -20,7 +20,10 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "oracle"))
 from nmpc_linesearch import LS_DEFAULTS, _barrier_value  # noqa: E402
 
-__all__ = ["LS_DEFAULTS", "merit", "line_search", "sqp_loop"]
+__all__ = ["LS_DEFAULTS", "merit", "line_search", "sqp_loop", "random_plan", "constant_plan", "walking_batch",
+           "NMPC_SEED"]
+
+NMPC_SEED = 26  # walking_batch's, chosen on the CPU: the host loops' smallest comparison margin is >= 1e-6
 
 
 def merit(srbd_model, p, plan, xs, us, N, Ac, bc):
@@ -113,3 +116,56 @@ def sqp_loop(srbd_model, oracle, p, plan, xs, us, x0, alpha, settings, sqp_max_l
         if conv:
             break
     return xs, us, alpha, it, conv, margin
+
+
+# ---- the plans several test modules share ----
+def random_plan(sm, p, B, N, seed, fields=("x_ref", "foot_r", "foot_l", "fz_max")):
+    """Distinct values for every robot and stage: references within +-0.3 of the default, feet
+    within +-0.15 m, fz_max in [50, 300] with a few swing stages at 1.0."""
+    rng = np.random.default_rng(seed)
+    x_ref = np.array(p.x_ref) + rng.uniform(-0.3, 0.3, size=(B, N + 1, 12))
+    foot_r = np.array(p.foot_r) + rng.uniform(-0.15, 0.15, size=(B, N, 3))
+    foot_l = np.array(p.foot_l) + rng.uniform(-0.15, 0.15, size=(B, N, 3))
+    fz = rng.uniform(50.0, 300.0, size=(B, N, 2))
+    swing = rng.uniform(size=(B, N, 2)) < 0.15
+    swing[0, 3, 0] = swing[B - 1, N - 1, 1] = True
+    fz[swing] = 1.0
+    full = dict(x_ref=x_ref, foot_r=foot_r, foot_l=foot_l, fz_max=fz)
+    return sm.SrbdPlan(**{k: (v if k in fields else None) for k, v in full.items()})
+
+
+def constant_plan(sm, p, B, N):
+    return sm.SrbdPlan(x_ref=np.tile(np.array(p.x_ref, dtype=np.float64), (B, N + 1, 1)),
+                       foot_r=np.tile(np.array(p.foot_r, dtype=np.float64), (B, N, 1)),
+                       foot_l=np.tile(np.array(p.foot_l, dtype=np.float64), (B, N, 1)),
+                       fz_max=np.full((B, N, 2), float(p.fmax)))
+
+
+def walking_batch(sm, p, B, N, seed):
+    """B robots, each with its own velocity command (a reference that moves at that velocity)
+    and a stepping pattern (feet that are set down ahead along the command, each foot
+    swinging -- fz_max = 1 -- for part of the horizon), from perturbed starts."""
+    rng = np.random.default_rng(seed)
+    xs, us, dx0 = sm.sample_trajectories(B, N, seed, p)
+    x0 = xs[:, 0] + dx0
+    k = np.arange(N + 1)
+    x_ref = np.tile(np.array(p.x_ref, dtype=np.float64), (B, N + 1, 1))
+    foot_r = np.tile(np.array(p.foot_r, dtype=np.float64), (B, N, 1))
+    foot_l = np.tile(np.array(p.foot_l, dtype=np.float64), (B, N, 1))
+    fz = np.empty((B, N, 2))
+    for i in range(B):
+        v = rng.uniform(-0.3, 0.3, size=2)  # commanded (vx, vy)
+        x_ref[i, :, 6:8] += np.outer(k * p.dt, v)
+        x_ref[i, :, 9:11] = v
+        x_ref[i] += rng.uniform(-0.01, 0.01, size=(N + 1, 12))
+        fz[i] = rng.uniform(150.0, 300.0, size=(N, 2))
+        s0 = int(rng.integers(2, 6))  # right foot swings s0 .. s0+4, left s0+9 .. s0+13
+        step = 10.0 * p.dt * v
+        for foot, lo in ((0, s0), (1, s0 + 9)):
+            f = foot_r if foot == 0 else foot_l
+            fz[i, lo:lo + 5, foot] = 1.0
+            f[i, lo + 5:, 0:2] += step  # set down ahead
+            f[i] += rng.uniform(-0.005, 0.005, size=(N, 3))
+    plan = sm.SrbdPlan(x_ref=x_ref, foot_r=foot_r, foot_l=foot_l, fz_max=fz)
+    alpha = np.where(np.arange(B) % 4 == 1, 0.5, 1.0)
+    return xs, us, x0, alpha, plan

@@ -1,17 +1,15 @@
-"""TEST INFRASTRUCTURE ONLY -- the terrains of the terrain tests, generated from seeds, and the
-host closed loop with terrain that the replanning device rollout is compared against: per tick
-srbd_model.gait_plan(terrain=...) from the measured state, then the host SQP loop of
-tests/nmpc_plan_host.py on that window, then srbd_model.plant_step and srbd_model.shift_guess
-(tests/gait_host.py's loop with the terrain under the planner)."""
+"""TEST INFRASTRUCTURE ONLY -- the terrains of the terrain tests, generated from seeds, what the
+planner selected on them restated from the planner without terrain, and the stairs the
+closed-loop tests walk up.  The host closed loop with the terrain under the planner is
+tests/rollout_host.py's closed_loop(gait=..., terrain=...)."""
 from __future__ import annotations
 
 import numpy as np
 
 import gait_host as GH
-import nmpc_plan_host as PH
 
-__all__ = ["flat0", "plane", "stairs", "rough", "lipschitz", "nominal", "selection", "closed_loop",
-           "stairs_terrain", "stairs_level", "stairs_case", "STAIRS"]
+__all__ = ["flat0", "plane", "stairs", "rough", "lipschitz", "nominal", "selection", "stairs_terrain",
+           "stairs_level", "stairs_case", "STAIRS"]
 
 
 # ---- the terrains: height arrays [ny][nx]; sample (j, i) lies at (x0 + i cell, y0 + j cell) ----
@@ -66,57 +64,6 @@ def selection(sm, p, gait, terrain, cmd, x, tick, ref_pose, foot_now, N, map_r=N
     maps = np.zeros(n.shape[0], dtype=np.int64) if maps is None else np.asarray(maps, dtype=np.int64)
     _, _, q, margin = sm.foothold_select(terrain, n, maps[:n.shape[0], None, None])
     return np.where(down, -1, q), np.where(down, np.inf, margin).min(initial=np.inf), n, down
-
-
-# ---- the host closed loop ----
-def closed_loop(sm, oracle, p, gait, terrain, cmd, xs, us, x, alpha, ref_pose, foot_now, ticks, settings,
-                sqp_max_loop, constraints="none", tick0=0, alpha_reset=0.0):
-    """gait_host.closed_loop with the terrain under the planner.  Returns its dict plus q_log
-    [B][ticks][2] (the chosen candidate of row 0's touchdown, -1 for a foot that is down),
-    select_margin (the smallest best-to-second-best cost gap over every touchdown of every tick)
-    and poses / feet (ref_pose and foot_now after each tick's planning step)."""
-    B, N = us.shape[0], us.shape[1]
-    xs, us, x = xs.copy(), us.copy(), x.copy()
-    alpha = np.array(alpha, dtype=np.float64)
-    ref_pose, foot_now = np.array(ref_pose, dtype=np.float64), np.array(foot_now, dtype=np.float64)
-    x_log = np.empty((B, ticks + 1, 12))
-    u_log = np.empty((B, ticks, 12))
-    it_log = np.zeros((B, ticks), dtype=np.int32)
-    cv_log = np.zeros((B, ticks), dtype=np.int32)
-    foot_log = np.empty((B, ticks, 2, 3))
-    fz_log = np.empty((B, ticks, 2))
-    q_log = np.empty((B, ticks, 2), dtype=np.int64)
-    x_log[:, 0] = x
-    margin, select_margin, steps, windows, poses, feet = np.inf, np.inf, [], [], [], []
-    for t in range(ticks):
-        q, m, _, _ = selection(sm, p, gait, terrain, cmd[:, t], x, tick0 + t, ref_pose, foot_now, N)
-        q_log[:, t], select_margin = q[:, 0], min(select_margin, m)
-        w, ref_pose, foot_now = sm.gait_plan(p, gait, cmd[:, t], x, tick0 + t, ref_pose, foot_now, N,
-                                             terrain=terrain)
-        windows.append(w)
-        poses.append(ref_pose)
-        feet.append(foot_now)
-        if alpha_reset > 0.0:
-            alpha[:] = alpha_reset
-        res = [PH.sqp_loop(sm, oracle, p, w.robot(i), xs[i], us[i], x[i], float(alpha[i]), settings,
-                           sqp_max_loop, constraints) for i in range(B)]
-        steps.append(res)
-        xs = np.stack([r[0] for r in res])
-        us = np.stack([r[1] for r in res])
-        alpha = np.array([r[2] for r in res], dtype=np.float64)
-        it_log[:, t] = [r[3] for r in res]
-        cv_log[:, t] = [int(r[4]) for r in res]
-        margin = min([margin] + [r[5] for r in res])
-        foot_log[:, t, 0], foot_log[:, t, 1], fz_log[:, t] = w.foot_r[:, 0], w.foot_l[:, 0], w.fz_max[:, 0]
-        u0 = us[:, 0].copy()
-        x = sm.plant_step(x, u0, p, w.foot_r[:, 0], w.foot_l[:, 0], None, 1)
-        xs, us = sm.shift_guess(xs, us, p, w)
-        u_log[:, t] = u0
-        x_log[:, t + 1] = x
-    return dict(x_log=x_log, u_log=u_log, sqp_iter=it_log, converged=cv_log, xs=xs, us=us, x=x, alpha=alpha,
-                margin=margin, steps=steps, foot_log=foot_log, fz_log=fz_log, ref_pose=ref_pose,
-                foot_now=foot_now, windows=windows, q_log=q_log, select_margin=select_margin,
-                poses=poses, feet=feet)
 
 
 # the stairs the closed-loop tests walk up: 2 cm cells, treads of three samples (6 cm), 3 cm risers

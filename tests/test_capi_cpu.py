@@ -23,6 +23,18 @@ def test_library_exports_every_declared_symbol(pkg):
         assert hasattr(L, s)
 
 
+def test_every_declared_function_has_a_prototype(pkg):
+    """The binding's table is the header's list of functions, none missing and none stale, and
+    lib() has applied it: a function left without argtypes would pass 64-bit pointers as C int."""
+    capi = pkg.capi
+    assert sorted(capi.PROTOTYPES) == capi.exported_symbols()
+    L = capi.lib()
+    for name, (restype, argtypes, _) in capi.PROTOTYPES.items():
+        f = getattr(L, name)
+        assert f.argtypes == argtypes and f.restype is restype, name
+        assert argtypes is not None and all(a is not None for a in argtypes), name
+
+
 def test_abi_version_and_strings(pkg):
     L = pkg.capi.lib()
     assert L.srbd_qp_abi_version() == 12

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import contact_host as CH
+import rollout_host as RH
 
 CONTACT_SYMBOLS = ("srbd_qp_srbd_set_contact_f64",)
 
@@ -235,7 +236,7 @@ def test_true_ground_moves_the_feet_in_contact(pkg):
     assert np.array_equal(x1, want[0]) and np.array_equal(ua, want[1])
     assert not np.array_equal(x1, sm.plant_step(x, u, p, fr, fl, contact=flat, in_contact=on)[0])
     # per-robot slices (tests/contact_host.py) are the batch
-    per = CH.plant_step(sm, [p] * B, x, u, fr, fl, contact=c, in_contact=on, state=CH.zero_state(B))
+    per = RH.plant_step(sm, [p] * B, x, u, fr, fl, contact=c, in_contact=on, state=CH.zero_state(B))
     whole = sm.plant_step(x, u, p, fr, fl, contact=c, in_contact=on, state=CH.zero_state(B))
     assert np.array_equal(per[0], whole[0]) and np.array_equal(per[1], whole[1])
     assert all(np.array_equal(per[2][k], whole[2][k]) for k in whole[2])

@@ -2,7 +2,8 @@
 the entry points exist and validate, and the host statement srbd_model.gait_plan has the
 properties include/srbd_qp.h states: a standing gait is the constant plan, the contact schedule
 is the integer formula, successive windows agree, the feedback moves the footholds and nothing
-else, and one tick of tests/gait_host.py's loop is gait_plan followed by the host SQP loop."""
+else, and one tick of tests/rollout_host.py's loop with a gait is gait_plan followed by the host
+SQP loop."""
 import ctypes as C
 import subprocess
 
@@ -11,18 +12,12 @@ import pytest
 
 import gait_host as GH
 import nmpc_plan_host as PH
+import rollout_host as RH
+from gait_host import rot
+from srbd_device import FIELDS, NMPC
 
 GAIT_SYMBOLS = ("srbd_qp_srbd_gait_plan_f64", "srbd_qp_srbd_rollout_gait_f64")
 EINVAL = -1  # SRBD_QP_EINVAL
-NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
-            tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
-            split_step=1)
-FIELDS = ("x_ref", "foot_r", "foot_l", "fz_max")
-
-
-def rot(yaw, v):
-    c, s = np.cos(yaw), np.sin(yaw)
-    return np.stack([c * v[..., 0] - s * v[..., 1], s * v[..., 0] + c * v[..., 1]], axis=-1)
 
 
 def feet_of(plan):
@@ -204,8 +199,8 @@ def test_one_tick_of_the_host_gait_loop_is_gait_plan_then_the_host_sqp_loop(pkg,
     B, N, T = 2, 6, 1
     p = sm.SrbdParams()
     xs, us, x, alpha, gait, cmd, ref_pose, foot_now = GH.walking_case(sm, p, B, N, T, 5)
-    out = GH.closed_loop(sm, oracle, p, gait, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, 15, "none",
-                         tick0=4, alpha_reset=alpha_reset)
+    out = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, 15, "none", p=p, gait=gait, cmd=cmd,
+                         ref_pose=ref_pose, foot_now=foot_now, tick0=4, alpha_reset=alpha_reset)
     w, pose, feet = sm.gait_plan(p, gait, cmd[:, 0], x, 4, ref_pose, foot_now, N)
     for k in FIELDS:
         assert np.array_equal(getattr(out["windows"][0], k), getattr(w, k)), k

@@ -3,7 +3,7 @@ against the host statement srbd_model.plant_step(contact=...): x at the rollout 
 the applied input, sat, fallen and alive exactly.  A cleared contact, a generous one, a robot
 fallen on entry and non-finite inputs against the plain advance (bit for bit where the header
 says so), and both rollouts against the caller's own loop (bit for bit) and the host closed loop
-of tests/contact_host.py.
+of tests/rollout_host.py with a contact.
 
 The fall thresholds are compared on values that carry rounding: every test that compares a fall
 with the host asserts, on the host result, that each tested robot's height above the ground and
@@ -18,32 +18,15 @@ import contact_host as CH
 import robots_host as RB
 import rollout_host as RH
 import terrain_host as TH
-from test_gpu_gait import caller_loop as gait_caller_loop, device_gait
-from test_gpu_plan import NMPC, SQP_MAX_LOOP, _dev, device_plan, handle
-from test_gpu_rollout import D_T, STEP_ATOL_U, STEP_ATOL_X, caller_loop, feet_plan, start
-from test_gpu_terrain import device_terrain
+from rollout_host import feet_plan, start
+from srbd_device import (NMPC, ROLLOUT_D_T as D_T, SQP_MAX_LOOP, STEP_ATOL_U, STEP_ATOL_X, _dev, caller_loop, close,
+                         device_contact, device_gait, device_plan, device_terrain, handle)
 
 pytestmark = pytest.mark.gpu
 
 B9 = 9  # four robots per block: two full blocks and a tail block of one
 FALL_MARGIN = 1e-6
 STATE = ("fallen", "alive", "sat")
-
-
-def close(got, want, what):  # tests/test_gpu_rollout.py:46, the rollout suite's tolerance for the same RK4
-    np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-11, atol=1e-12 * max(np.abs(want).max(), 1.0),
-                               err_msg=str(what))
-
-
-def device_contact(capi, c, state=None):
-    """(capi.Contact of a srbd_model.SrbdContact, the device state): `state` as contact_host's
-    dicts (None: no arrays); sat travels as int32, the same 32 bits."""
-    import torch
-    st = {k: torch.from_numpy(np.ascontiguousarray(v).astype(np.int32)).cuda() for k, v in (state or {}).items()}
-    return capi.Contact(mu=c.mu, mu_r=None if c.mu_r is None else _dev(np.asarray(c.mu_r, dtype=np.float64)),
-                        Lt=c.Lt, fz_hi=c.fz_hi, fz_contact=c.fz_contact, ground_z=c.ground_z,
-                        ground=None if c.ground is None else device_terrain(capi, c.ground), z_min=c.z_min,
-                        cos_tilt_min=c.cos_tilt_min, **st), st
 
 
 def state_of(st):
@@ -97,7 +80,7 @@ def host_advance(sm, p, xs, us, x, plan, plant, wrench, contact, substeps, state
     state went through the fall test."""
     B = x.shape[0]
     on = sm.contact_flags(contact, None if plan is None or plan.fz_max is None else plan.fz_max[:, 0], B)
-    x1, ua, st = CH.plant_step(sm, plant if plant is not None else p, x, us[:, 0], None if plan is None else plan.foot_r[:, 0],
+    x1, ua, st = RH.plant_step(sm, plant if plant is not None else p, x, us[:, 0], None if plan is None else plan.foot_r[:, 0],
                                None if plan is None else plan.foot_l[:, 0], wrench, substeps, contact=contact,
                                in_contact=on, state=state)
     xs1, us1 = sm.shift_guess(xs, us, p, plan)
@@ -295,7 +278,8 @@ def test_rollout_with_a_contact(pkg, oracle):
     import torch
     capi, sm = pkg.capi, pkg.srbd_model
     B, N, T, p, xs, us, x, alpha, plan, contact = rollout_case(sm)
-    host = CH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, contact, alpha_reset=1.0)
+    host = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, "none", p=p, plan=plan, contact=contact,
+                          alpha_reset=1.0)
     assert host["margin"] >= 1e-6, host["margin"]
     standing = np.ones(B, dtype=bool)
     for t in range(T):  # the robots tested at tick t are those that stood before it
@@ -314,7 +298,7 @@ def test_rollout_with_a_contact(pkg, oracle):
     ct, st_b = device_contact(capi, contact, CH.zero_state(B))
     h.set_contact(ct)
     b = [_dev(v) for v in (xs, us, x, alpha)]
-    logs_b = caller_loop(capi, h, B, N, T, "none", *b, plan_t, None, 1, 1.0)
+    logs_b = caller_loop(capi, h, B, N, T, "none", *b, None, 1, 1.0, plan_t=plan_t)
     names = ("xs", "us", "x", "alpha", "x_log", "u_log", "sqp_iter_log", "converged_log")
     for name, u, v in zip(names, a + list(logs_a), b + list(logs_b)):
         assert bool(torch.isfinite(u.double()).all()), name
@@ -366,7 +350,8 @@ def test_gait_rollout_with_a_true_ground_is_the_callers_loop_bit_for_bit(pkg):
         h.set_contact(ct)
         v = [_dev(w) for w in (xs, us, x, alpha, ref_pose, foot_now)]
         if loop:
-            logs = gait_caller_loop(capi, h, gait_t, B, N, T, tick0, "none", cmd_t, *v, wrench_t, 1, 0.0)
+            logs = caller_loop(capi, h, B, N, T, "none", *v[:4], wrench_t, 1, 0.0, gait_t=gait_t, cmd_t=cmd_t,
+                               pose=v[4], feet=v[5], tick0=tick0)
         else:
             logs = capi.srbd_rollout_gait(h, gait_t, cmd_t, *v, T, tick0, "none", NMPC, SQP_MAX_LOOP, wrench=wrench_t)
         runs.append((v + list(logs), state_of(st)))

@@ -2,39 +2,19 @@
 command, a gait and the measured state; srbd_qp_srbd_rollout_gait_f64: the closed loop that
 replans every tick) against the host statement srbd_model.gait_plan, against the caller's own
 loop over the three public entry points (bit for bit) and against the host closed loop of
-tests/gait_host.py."""
+tests/rollout_host.py with a gait."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import gait_host as GH
-from test_gpu_plan import NMPC, SQP_MAX_LOOP, _dev, constant_plan, device_plan, handle
+import rollout_host as RH
+from nmpc_plan_host import constant_plan
+from srbd_device import (FIELDS, NMPC, SQP_MAX_LOOP, STEP_ATOL_U, STEP_ATOL_X, _dev, caller_loop, close, device_gait,
+                         device_plan, handle)
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("x_ref", "foot_r", "foot_l", "fz_max")
-
-
-def device_gait(capi, g):
-    """capi.Gait of a srbd_model.SrbdGait: an integer field given per robot (period [B], swing /
-    offset [B][2]) becomes an int32 device tensor (the struct's _r array), one given for every
-    robot stays the scalars."""
-    import torch
-    ints = {}
-    for name, rank in (("period", 1), ("swing", 2), ("offset", 2)):
-        v = np.asarray(getattr(g, name))
-        if v.ndim == rank:
-            ints[name] = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).cuda()
-        else:
-            ints[name] = int(v) if rank == 1 else tuple(int(e) for e in v)
-    return capi.Gait(hip=g.hip, ground_z=g.ground_z, k_raibert=g.k_raibert, fz_stance=g.fz_stance,
-                     fz_swing=g.fz_swing, anchor=g.anchor, **ints)
-
-
-def close(got, want, what):  # test_advance_matches_the_host_model's: one sincos and <= N + 1 additions
-    np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-11, atol=1e-12 * max(np.abs(want).max(), 1.0),
-                               err_msg=str(what))
 
 
 # ---- 1. the planner against the host statement ----
@@ -139,27 +119,6 @@ def test_standing_gait_is_the_constant_plan_on_the_device(pkg, N):
 
 
 # ---- 3. the replanning rollout is the caller's loop over the three entry points, bit for bit ----
-def caller_loop(capi, h, gait_t, B, N, T, tick0, constraints, cmd_t, xs, us, x, alpha, pose, feet, wrench_t,
-                substeps, alpha_reset):
-    import torch
-    f = dict(dtype=torch.float64, device="cuda")
-    x_log, u_log = torch.zeros(B, T + 1, 12, **f), torch.zeros(B, T, 12, **f)
-    it_log = torch.zeros(B, T, dtype=torch.int32, device="cuda")
-    cv_log = torch.zeros(B, T, dtype=torch.int32, device="cuda")
-    foot_log, fz_log = torch.zeros(B, T, 2, 3, **f), torch.zeros(B, T, 2, **f)
-    x_log[:, 0] = x
-    for t in range(T):
-        w = capi.srbd_gait_plan(h, gait_t, cmd_t[:, t].contiguous(), x, tick0 + t, pose, feet)
-        if alpha_reset > 0.0:
-            alpha.fill_(alpha_reset)
-        it, cv = capi.srbd_nmpc(h, xs, us, x, alpha, constraints, NMPC, SQP_MAX_LOOP, plan=w)
-        foot_log[:, t, 0], foot_log[:, t, 1], fz_log[:, t] = w.foot_r[:, 0], w.foot_l[:, 0], w.fz_max[:, 0]
-        u0 = capi.srbd_advance(h, xs, us, x=x, plan=w, wrench=wrench_t[:, t].contiguous(), substeps=substeps)
-        h.synchronize()
-        it_log[:, t], cv_log[:, t], u_log[:, t], x_log[:, t + 1] = it, cv, u0, x
-    return x_log, u_log, it_log, cv_log, foot_log, fz_log
-
-
 @pytest.mark.parametrize("alpha_reset", [0.0, 1.0])
 @pytest.mark.parametrize("constraints", ["none", "box_u", "cone"])
 def test_gait_rollout_is_the_callers_loop_bit_for_bit(pkg, constraints, alpha_reset):
@@ -177,7 +136,8 @@ def test_gait_rollout_is_the_callers_loop_bit_for_bit(pkg, constraints, alpha_re
         logs_a = capi.srbd_rollout_gait(h, gait_t, cmd_t, *a, T, tick0, constraints, NMPC, SQP_MAX_LOOP,
                                         wrench=wrench_t, substeps=2, alpha_reset=alpha_reset)
         b = [_dev(v) for v in (xs, us, x, alpha, ref_pose, foot_now)]
-        logs_b = caller_loop(capi, h, gait_t, B, N, T, tick0, constraints, cmd_t, *b, wrench_t, 2, alpha_reset)
+        logs_b = caller_loop(capi, h, B, N, T, constraints, *b[:4], wrench_t, 2, alpha_reset, gait_t=gait_t,
+                             cmd_t=cmd_t, pose=b[4], feet=b[5], tick0=tick0)
         names = ("xs", "us", "x", "alpha", "ref_pose", "foot_now", "x_log", "u_log", "sqp_iter_log",
                  "converged_log", "foot_log", "fz_log")
         for name, u, v in zip(names, a + list(logs_a), b + list(logs_b)):
@@ -219,7 +179,6 @@ D_T = {
     ("box_u", 0.0): ((3.3e-07, 5.7e-07, 7.1e-07, 7.6e-07), (2.9e-05, 2.3e-05, 1.8e-05, 1.4e-05)),
     ("box_u", 1.0): ((3.3e-07, 5.7e-07, 7.1e-07, 7.6e-07), (2.9e-05, 2.3e-05, 1.8e-05, 1.4e-05)),
 }
-STEP_ATOL_X, STEP_ATOL_U = 1e-9, 1e-6  # the step test's (tests/test_gpu_plan.py test 5)
 
 
 @pytest.mark.parametrize("alpha_reset", [0.0, 1.0])
@@ -229,8 +188,8 @@ def test_gait_rollout_matches_the_host_gait_loop(pkg, oracle, constraints, alpha
     B, N, T = 4, 10, 4
     p = sm.SrbdParams()
     xs, us, x, alpha, gait, cmd, ref_pose, foot_now = GH.walking_case(sm, p, B, N, T, GAIT_SEED)
-    host = GH.closed_loop(sm, oracle, p, gait, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, SQP_MAX_LOOP,
-                          constraints, alpha_reset=alpha_reset)
+    host = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, constraints, p=p, gait=gait, cmd=cmd,
+                          ref_pose=ref_pose, foot_now=foot_now, alpha_reset=alpha_reset)
     # conditions on the inputs: no host decision on a boundary, robots that stop at different
     # iterations, and every robot has a liftoff and a touchdown inside the four ticks
     assert host["margin"] >= 1e-6, host["margin"]

@@ -8,52 +8,10 @@ import numpy as np
 import pytest
 
 import nmpc_plan_host as PH
+from nmpc_plan_host import NMPC_SEED, constant_plan, random_plan, walking_batch
+from srbd_device import NMPC, SQP_MAX_LOOP, _dev, device_plan, handle, host_nmpc
 
 pytestmark = pytest.mark.gpu
-
-# NMPC_solver.cpp:70-82, as tests/test_gpu_nmpc.py
-NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
-            tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
-            split_step=1)
-SQP_MAX_LOOP = 15
-NMPC_SEED = 26  # chosen on the CPU: the host loops' smallest comparison margin is >= 1e-6 (test 5)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def random_plan(sm, p, B, N, seed, fields=("x_ref", "foot_r", "foot_l", "fz_max")):
-    """Distinct values for every robot and stage: references within +-0.3 of the default, feet
-    within +-0.15 m, fz_max in [50, 300] with a few swing stages at 1.0."""
-    rng = np.random.default_rng(seed)
-    x_ref = np.array(p.x_ref) + rng.uniform(-0.3, 0.3, size=(B, N + 1, 12))
-    foot_r = np.array(p.foot_r) + rng.uniform(-0.15, 0.15, size=(B, N, 3))
-    foot_l = np.array(p.foot_l) + rng.uniform(-0.15, 0.15, size=(B, N, 3))
-    fz = rng.uniform(50.0, 300.0, size=(B, N, 2))
-    swing = rng.uniform(size=(B, N, 2)) < 0.15
-    swing[0, 3, 0] = swing[B - 1, N - 1, 1] = True
-    fz[swing] = 1.0
-    full = dict(x_ref=x_ref, foot_r=foot_r, foot_l=foot_l, fz_max=fz)
-    return sm.SrbdPlan(**{k: (v if k in fields else None) for k, v in full.items()})
-
-
-def constant_plan(sm, p, B, N):
-    return sm.SrbdPlan(x_ref=np.tile(np.array(p.x_ref, dtype=np.float64), (B, N + 1, 1)),
-                       foot_r=np.tile(np.array(p.foot_r, dtype=np.float64), (B, N, 1)),
-                       foot_l=np.tile(np.array(p.foot_l, dtype=np.float64), (B, N, 1)),
-                       fz_max=np.full((B, N, 2), float(p.fmax)))
-
-
-def device_plan(capi, plan):
-    return capi.Plan(**{k: (None if getattr(plan, k) is None else _dev(getattr(plan, k)))
-                        for k in ("x_ref", "foot_r", "foot_l", "fz_max")})
-
-
-def handle(capi, N, B, constraints):
-    return capi.Handle(N, 12, 12, 24 if constraints == "cone" else 0, constraints == "box_u", False,
-                       capacity=B)
 
 
 def check_linearize(pkg, B, N, seed, constraints, plan):
@@ -186,42 +144,6 @@ def test_partial_plans(pkg, field):
 
 
 # ---- 5. the NMPC step ----
-def walking_batch(sm, p, B, N, seed):
-    """B robots, each with its own velocity command (a reference that moves at that velocity)
-    and a stepping pattern (feet that are set down ahead along the command, each foot
-    swinging -- fz_max = 1 -- for part of the horizon), from perturbed starts."""
-    rng = np.random.default_rng(seed)
-    xs, us, dx0 = sm.sample_trajectories(B, N, seed, p)
-    x0 = xs[:, 0] + dx0
-    k = np.arange(N + 1)
-    x_ref = np.tile(np.array(p.x_ref, dtype=np.float64), (B, N + 1, 1))
-    foot_r = np.tile(np.array(p.foot_r, dtype=np.float64), (B, N, 1))
-    foot_l = np.tile(np.array(p.foot_l, dtype=np.float64), (B, N, 1))
-    fz = np.empty((B, N, 2))
-    for i in range(B):
-        v = rng.uniform(-0.3, 0.3, size=2)  # commanded (vx, vy)
-        x_ref[i, :, 6:8] += np.outer(k * p.dt, v)
-        x_ref[i, :, 9:11] = v
-        x_ref[i] += rng.uniform(-0.01, 0.01, size=(N + 1, 12))
-        fz[i] = rng.uniform(150.0, 300.0, size=(N, 2))
-        s0 = int(rng.integers(2, 6))  # right foot swings s0 .. s0+4, left s0+9 .. s0+13
-        step = 10.0 * p.dt * v
-        for foot, lo in ((0, s0), (1, s0 + 9)):
-            f = foot_r if foot == 0 else foot_l
-            fz[i, lo:lo + 5, foot] = 1.0
-            f[i, lo + 5:, 0:2] += step  # set down ahead
-            f[i] += rng.uniform(-0.005, 0.005, size=(N, 3))
-    plan = sm.SrbdPlan(x_ref=x_ref, foot_r=foot_r, foot_l=foot_l, fz_max=fz)
-    alpha = np.where(np.arange(B) % 4 == 1, 0.5, 1.0)
-    return xs, us, x0, alpha, plan
-
-
-def host_nmpc(sm, oracle, p, batch, constraints):
-    xs, us, x0, alpha, plan = batch
-    return [PH.sqp_loop(sm, oracle, p, plan.robot(i), xs[i], us[i], x0[i], float(alpha[i]), NMPC,
-                        SQP_MAX_LOOP, constraints) for i in range(xs.shape[0])]
-
-
 @pytest.mark.parametrize("constraints", ["none", "box_u"])
 def test_nmpc_step_with_a_plan_matches_the_host_loop(pkg, oracle, constraints):
     sm = pkg.srbd_model

@@ -1,6 +1,6 @@
 """Per-robot model and plant parameters on the device (srbd_qp_srbd_set_robots_f64: the MODEL
 role is what the controller believes, the PLANT role the true robot) against the host model
-called once per robot with that robot's SrbdParams (tests/robots_host.py)."""
+called once per robot with that robot's SrbdParams (tests/robots_host.py, tests/rollout_host.py)."""
 import dataclasses
 
 import numpy as np
@@ -8,15 +8,12 @@ import pytest
 
 import robots_host as BH
 import rollout_host as RH
-from test_gpu_plan import (NMPC, NMPC_SEED, SQP_MAX_LOOP, _dev, device_plan, handle, host_nmpc, random_plan,
-                           walking_batch)
-from test_gpu_rollout import caller_loop, feet_plan, start
+from nmpc_plan_host import NMPC_SEED, random_plan, walking_batch
+from rollout_host import feet_plan, start
+from srbd_device import (NMPC, SQP_MAX_LOOP, STEP_ATOL_U, STEP_ATOL_X, _dev, caller_loop, close, device_plan,
+                         device_robots, handle, host_nmpc)
 
 pytestmark = pytest.mark.gpu
-
-
-def device_robots(capi, params, fields=BH.MODEL_FIELDS):
-    return capi.Robots(**{k: _dev(v) for k, v in BH.arrays(params, fields).items()})
 
 
 def check_linearize(pkg, B, N, seed, constraints, params, robots_t, plan=None):
@@ -233,7 +230,7 @@ def test_nmpc_step_with_robots_matches_the_host_loop(pkg, oracle, constraints):
     batch = walking_batch(sm, p, B, N, NMPC_SEED)
     xs, us, x0, alpha, plan = batch
     params = BH.draw(p, B, ROBOTS_SEED)
-    host = BH.sqp_loops(sm, oracle, params, plan, xs, us, x0, alpha, NMPC, SQP_MAX_LOOP, constraints)
+    host = RH.sqp_loops(sm, oracle, params, plan, xs, us, x0, alpha, NMPC, SQP_MAX_LOOP, constraints)
     nominal = host_nmpc(sm, oracle, p, batch, constraints)
     print("host iterations", [r[3] for r in host], "nominal", [r[3] for r in nominal],
           "margin", min(r[5] for r in host))
@@ -272,10 +269,6 @@ def test_advance_moves_the_plant_with_the_plant_role_and_the_guess_with_the_mode
     model_t, plant_t = device_robots(capi, model), device_robots(capi, plant, BH.PLANT_FIELDS)
     h = handle(capi, N, B, "none")
 
-    def close(got, want, what):  # the linearisation test's tolerance for the same RK4
-        np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-11,
-                                   atol=1e-12 * max(np.abs(want).max(), 1.0), err_msg=str(what))
-
     def advance(w):
         xs_t, us_t, x_t = _dev(xs), _dev(us), _dev(x)
         u0 = capi.srbd_advance(h, xs_t, us_t, x=x_t, plan=plan_t, wrench=None if w is None else _dev(w),
@@ -288,7 +281,7 @@ def test_advance_moves_the_plant_with_the_plant_role_and_the_guess_with_the_mode
         assert torch.equal(us_t[:, N - 1], _dev(us[:, N - 1]))
         return xs_t, x_t
 
-    want_xs, _ = BH.shift_guess(sm, model, xs, us, plan)
+    want_xs, _ = RH.shift_guess(sm, model, xs, us, plan)
     # the plant's parameters: the PLANT role, or the MODEL role where the PLANT role has none
     mixed = [dataclasses.replace(m, mass=q.mass) for m, q in zip(model, plant)]
     for what, roles, truth in (("both roles", dict(model=model_t, plant=plant_t), plant),
@@ -297,7 +290,7 @@ def test_advance_moves_the_plant_with_the_plant_role_and_the_guess_with_the_mode
                                 mixed)):
         h.set_robots(**roles)
         xs_t, x_t = advance(wrench)
-        close(x_t, BH.plant_step(sm, truth, x, us[:, 0], plan.foot_r[:, 0], plan.foot_l[:, 0], wrench, substeps),
+        close(x_t, RH.plant_step(sm, truth, x, us[:, 0], plan.foot_r[:, 0], plan.foot_l[:, 0], wrench, substeps),
               (what, "x"))
         close(xs_t[:, N], want_xs[:, N], (what, "xs[N]"))
         # a pure force moves the velocity rows by dt F / the true robot's mass
@@ -310,9 +303,9 @@ def test_advance_moves_the_plant_with_the_plant_role_and_the_guess_with_the_mode
     xs_t, x_t = advance(wrench)
     nominal = [p] * B
     truth = [dataclasses.replace(p, mass=q.mass, Lbody=q.Lbody) for q in plant]
-    close(x_t, BH.plant_step(sm, truth, x, us[:, 0], plan.foot_r[:, 0], plan.foot_l[:, 0], wrench, substeps),
+    close(x_t, RH.plant_step(sm, truth, x, us[:, 0], plan.foot_r[:, 0], plan.foot_l[:, 0], wrench, substeps),
           "plant only, x")
-    close(xs_t[:, N], BH.shift_guess(sm, nominal, xs, us, plan)[0][:, N], "plant only, xs[N]")
+    close(xs_t[:, N], RH.shift_guess(sm, nominal, xs, us, plan)[0][:, N], "plant only, xs[N]")
 
 
 # ---- 7. the rollout ----
@@ -327,7 +320,6 @@ D_T = {
     ("box_u", 0.0): ((2.9e-07, 5.3e-07, 7.7e-07, 9.0e-07), (1.6e-05, 1.1e-05, 8.4e-06, 6.3e-06)),
     ("box_u", 1.0): ((2.9e-07, 5.3e-07, 7.7e-07, 9.0e-07), (1.6e-05, 1.1e-05, 8.4e-06, 6.3e-06)),
 }
-STEP_ATOL_X, STEP_ATOL_U = 1e-9, 1e-6  # the step test's (test 5)
 
 
 @pytest.mark.parametrize("alpha_reset", [0.0, 1.0])
@@ -340,8 +332,8 @@ def test_rollout_with_robots(pkg, oracle, constraints, alpha_reset):
     xs, us, x, alpha, plan = RH.walking_case(sm, p, B, N, T, ROLLOUT_SEED)
     model = BH.draw(p, B, ROLLOUT_SEED + 100)
     plant = BH.draw_plant(model, ROLLOUT_SEED + 200)
-    loop = lambda true: BH.closed_loop(sm, oracle, model, true, plan, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP,
-                                       constraints, substeps=substeps, alpha_reset=alpha_reset)
+    loop = lambda true: RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, constraints, model=model,
+                                       plant=true, plan=plan, substeps=substeps, alpha_reset=alpha_reset)
     host = loop(plant)
     # conditions on the inputs: no host decision on a boundary, and a mismatch that matters
     assert host["margin"] >= 1e-6, host["margin"]
@@ -357,7 +349,7 @@ def test_rollout_with_robots(pkg, oracle, constraints, alpha_reset):
     logs_a = capi.srbd_rollout(h, *a, T, constraints, NMPC, SQP_MAX_LOOP, plan=plan_t, substeps=substeps,
                                alpha_reset=alpha_reset)
     b = [_dev(v) for v in (xs, us, x, alpha)]
-    logs_b = caller_loop(capi, h2, B, N, T, constraints, *b, plan_t, None, substeps, alpha_reset)
+    logs_b = caller_loop(capi, h2, B, N, T, constraints, *b, None, substeps, alpha_reset, plan_t=plan_t)
     names = ("xs", "us", "x", "alpha", "x_log", "u_log", "sqp_iter_log", "converged_log")
     for name, u, v in zip(names, a + list(logs_a), b + list(logs_b)):
         assert bool(torch.isfinite(u.double()).all()), name

@@ -6,25 +6,12 @@ import numpy as np
 import pytest
 
 import rollout_host as RH
-from test_gpu_plan import NMPC, SQP_MAX_LOOP, _dev, device_plan, handle, random_plan
+from nmpc_plan_host import random_plan
+from rollout_host import feet_plan, start
+from srbd_device import (NMPC, ROLLOUT_D_T as D_T, SQP_MAX_LOOP, STEP_ATOL_U, STEP_ATOL_X, _dev, caller_loop, close,
+                         device_plan, handle)
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("x_ref", "foot_r", "foot_l", "fz_max")
-
-
-def start(sm, p, B, N, seed):
-    xs, us, dx0 = sm.sample_trajectories(B, N, seed, p)
-    return xs, us, xs[:, 0] + dx0
-
-
-def feet_plan(sm, p, B, N, seed):
-    """random_plan's values for any N >= 1 (random_plan marks swing stages that need N >= 4)."""
-    rng = np.random.default_rng(seed)
-    return sm.SrbdPlan(x_ref=np.array(p.x_ref) + rng.uniform(-0.3, 0.3, size=(B, N + 1, 12)),
-                       foot_r=np.array(p.foot_r) + rng.uniform(-0.15, 0.15, size=(B, N, 3)),
-                       foot_l=np.array(p.foot_l) + rng.uniform(-0.15, 0.15, size=(B, N, 3)),
-                       fz_max=rng.uniform(50.0, 300.0, size=(B, N, 2)))
 
 
 # ---- 1. one tick against the host model ----
@@ -41,11 +28,6 @@ def test_advance_matches_the_host_model(pkg, N):
     plan_t = device_plan(capi, plan)
     wrench = np.random.default_rng(22).uniform(-20.0, 20.0, size=(B, 6))
     h = handle(capi, N, B, "none")
-
-    def close(got, want, what):  # the linearisation test's tolerance for the same RK4
-        np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-11,
-                                   atol=1e-12 * max(np.abs(want).max(), 1.0), err_msg=str(what))
-
     for substeps in (1, 4):
         for use_w in (False, True):
             for use_plan in (True, False):
@@ -76,30 +58,6 @@ def test_advance_matches_the_host_model(pkg, N):
 
 
 # ---- 2. a rollout is the caller's loop over the two public entry points, bit for bit ----
-def caller_loop(capi, h, B, N, T, constraints, xs, us, x, alpha, plan_t, wrench_t, substeps, alpha_reset):
-    """Steps 1-6 of srbd_qp_srbd_rollout_f64's contract through srbd_nmpc and srbd_advance."""
-    import torch
-    x_log = torch.zeros(B, T + 1, 12, dtype=torch.float64, device="cuda")
-    u_log = torch.zeros(B, T, 12, dtype=torch.float64, device="cuda")
-    it_log = torch.zeros(B, T, dtype=torch.int32, device="cuda")
-    cv_log = torch.zeros(B, T, dtype=torch.int32, device="cuda")
-    x_log[:, 0] = x
-    for t in range(T):
-        w = None
-        if plan_t is not None:
-            w = capi.Plan(**{k: (None if getattr(plan_t, k) is None else
-                                 getattr(plan_t, k)[:, t:t + N + (k == "x_ref")].contiguous()) for k in FIELDS})
-        if alpha_reset > 0.0:
-            alpha.fill_(alpha_reset)
-        it, cv = capi.srbd_nmpc(h, xs, us, x, alpha, constraints, NMPC, SQP_MAX_LOOP, plan=w)
-        u0 = capi.srbd_advance(h, xs, us, x=x, plan=w,
-                               wrench=None if wrench_t is None else wrench_t[:, t].contiguous(),
-                               substeps=substeps)
-        h.synchronize()
-        it_log[:, t], cv_log[:, t], u_log[:, t], x_log[:, t + 1] = it, cv, u0, x
-    return x_log, u_log, it_log, cv_log
-
-
 @pytest.mark.parametrize("alpha_reset", [0.0, 1.0])
 @pytest.mark.parametrize("constraints", ["none", "box_u", "cone"])
 def test_rollout_is_the_callers_loop_bit_for_bit(pkg, constraints, alpha_reset):
@@ -118,7 +76,7 @@ def test_rollout_is_the_callers_loop_bit_for_bit(pkg, constraints, alpha_reset):
         logs_a = capi.srbd_rollout(h, *a, T, constraints, NMPC, SQP_MAX_LOOP, plan=plan_t, plan_stages=P,
                                    wrench=wrench_t, substeps=2, alpha_reset=alpha_reset)
         b = [_dev(v) for v in (xs, us, x, alpha)]
-        logs_b = caller_loop(capi, h, B, N, T, constraints, *b, plan_t, wrench_t, 2, alpha_reset)
+        logs_b = caller_loop(capi, h, B, N, T, constraints, *b, wrench_t, 2, alpha_reset, plan_t=plan_t)
         names = ("xs", "us", "x", "alpha", "x_log", "u_log", "sqp_iter_log", "converged_log")
         for name, u, v in zip(names, a + list(logs_a), b + list(logs_b)):
             assert bool(torch.isfinite(u.double()).all()), (T, name)
@@ -147,17 +105,7 @@ def test_rollout_of_zero_ticks_touches_nothing(pkg):
 # ticks is >= 1e-6 and at least two distinct SQP iteration counts occur, in all four cases below
 # (both are asserted).
 ROLLOUT_SEED = 30  # scripts/rollout_sensitivity.py --search 24 34: margins 3.3e-6 (none), 4.5e-6 (box_u)
-# d_t: the largest change of the host loop's x_log[t] / u_log[t-1] when the loop
-# is rerun with x, xs, us perturbed by relative 1e-7 -- the largest device-host gap the step
-# test's tolerance admits after one step -- measured on the CPU (scripts/rollout_sensitivity.py)
-# per case (constraints, alpha_reset), t = 1..4: (d_t of x, d_t of u).
-D_T = {
-    ("none", 0.0): ((2.7e-07, 5.1e-07, 7.4e-07, 8.3e-07), (2.3e-05, 1.7e-05, 1.4e-05, 8.8e-06)),
-    ("none", 1.0): ((2.7e-07, 5.1e-07, 7.4e-07, 8.3e-07), (2.3e-05, 1.7e-05, 1.4e-05, 8.8e-06)),
-    ("box_u", 0.0): ((2.8e-07, 5.3e-07, 7.7e-07, 8.5e-07), (2.4e-05, 1.7e-05, 1.4e-05, 8.7e-06)),
-    ("box_u", 1.0): ((2.8e-07, 5.3e-07, 7.7e-07, 8.5e-07), (2.3e-05, 1.7e-05, 1.4e-05, 8.7e-06)),
-}
-STEP_ATOL_X, STEP_ATOL_U = 1e-9, 1e-6  # the step test's (tests/test_gpu_plan.py test 5)
+# D_T and the step tolerances: tests/srbd_device.py
 
 
 @pytest.mark.parametrize("alpha_reset", [0.0, 1.0])
@@ -167,7 +115,7 @@ def test_rollout_matches_the_host_closed_loop(pkg, oracle, constraints, alpha_re
     B, N, T = 4, 10, 4
     p = sm.SrbdParams()
     xs, us, x, alpha, plan = RH.walking_case(sm, p, B, N, T, ROLLOUT_SEED)
-    host = RH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, constraints,
+    host = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, constraints, p=p, plan=plan,
                           alpha_reset=alpha_reset)
     # conditions on the inputs: no host decision on a boundary, and robots that stop at different
     # iterations

@@ -2,31 +2,24 @@
 srbd_qp_srbd_terrain_height_f64): the sampler and the planner against the host statement
 srbd_model.terrain_height / gait_plan(terrain=...), flat ground and a cleared terrain against the
 planner without (bit for bit), a plane against its closed form, the replanning rollout against
-the caller's own loop (bit for bit) and against the host closed loop of tests/terrain_host.py."""
+the caller's own loop (bit for bit) and against the host closed loop of tests/rollout_host.py
+with a gait and the terrain."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import gait_host as GH
+import rollout_host as RH
 import terrain_host as TH
-from test_gpu_gait import FIELDS, STEP_ATOL_U, STEP_ATOL_X, caller_loop, close, device_gait
-from test_gpu_plan import NMPC, SQP_MAX_LOOP, _dev, handle
+from srbd_device import (FIELDS, NMPC, SQP_MAX_LOOP, STEP_ATOL_U, STEP_ATOL_X, _dev, caller_loop, close, device_gait,
+                         device_terrain, handle)
 
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 1e-11, 1e-12  # `close`'s: rtol, and atol per max(|want|, 1)
 # the two map shapes, neither square: (ny, nx, x0, y0, cell) around the robots' start
 GRIDS = ((7, 12, 0.1, -0.25, 0.08), (9, 5, 0.3, -0.4, 0.1))
-
-
-def device_terrain(capi, t, map_r=None):
-    """capi.Terrain of a srbd_model.SrbdTerrain."""
-    import torch
-    m = t.map_r if map_r is None else map_r
-    return capi.Terrain(_dev(np.asarray(t.height, dtype=np.float64)), t.x0, t.y0, t.cell,
-                        map_r=None if m is None else torch.from_numpy(np.asarray(m, dtype=np.int32)).cuda(),
-                        search=t.search, w_rough=t.w_rough)
 
 
 def tol(want):
@@ -246,7 +239,8 @@ def test_terrain_rollout_is_the_callers_loop_bit_for_bit(pkg, constraints):
     a = [_dev(v) for v in (xs, us, x, alpha, ref_pose, foot_now)]
     logs_a = capi.srbd_rollout_gait(h, gait_t, cmd_t, *a, T, tick0, constraints, NMPC, SQP_MAX_LOOP, wrench=wrench_t)
     b = [_dev(v) for v in (xs, us, x, alpha, ref_pose, foot_now)]
-    logs_b = caller_loop(capi, h, gait_t, B, N, T, tick0, constraints, cmd_t, *b, wrench_t, 1, 0.0)
+    logs_b = caller_loop(capi, h, B, N, T, constraints, *b[:4], wrench_t, 1, 0.0, gait_t=gait_t, cmd_t=cmd_t,
+                         pose=b[4], feet=b[5], tick0=tick0)
     names = ("xs", "us", "x", "alpha", "ref_pose", "foot_now", "x_log", "u_log", "sqp_iter_log", "converged_log",
              "foot_log", "fz_log")
     for name, u, v in zip(names, a + list(logs_a), b + list(logs_b)):
@@ -285,8 +279,8 @@ def test_terrain_rollout_matches_the_host_terrain_loop(pkg, oracle, constraints)
     xs, us, x, alpha, gait, cmd, ref_pose, foot_now = TH.stairs_case(sm, p, B, N, T, STAIRS_SEED)
     ter = TH.stairs_terrain(sm, search=1)
     cell, rise = ter.cell, TH.STAIRS["rise"]
-    host = TH.closed_loop(sm, oracle, p, gait, ter, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, SQP_MAX_LOOP,
-                          constraints)
+    host = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, SQP_MAX_LOOP, constraints, p=p, gait=gait, cmd=cmd,
+                          ref_pose=ref_pose, foot_now=foot_now, terrain=ter)
     assert host["margin"] >= 1e-6, host["margin"]
     assert host["select_margin"] >= MIN_MARGIN * cell ** 2, host["select_margin"] / cell ** 2
     assert len(set(host["sqp_iter"].ravel().tolist())) >= 2, host["sqp_iter"]

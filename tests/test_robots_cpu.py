@@ -1,7 +1,7 @@
 """Per-robot model and plant parameters (srbd_qp_srbd_set_robots_f64) without a GPU: the entry
 point exists and validates, the binding checks its tensors before the library sees them, and
-the per-robot host closed loop of tests/robots_host.py is tests/rollout_host.py's when every
-robot has the same parameters."""
+tests/rollout_host.py's closed loop with per-robot lists is the loop with one SrbdParams when
+every robot has the same parameters."""
 import ctypes as C
 import dataclasses
 import subprocess
@@ -11,12 +11,9 @@ import pytest
 
 import robots_host as BH
 import rollout_host as RH
+from srbd_device import NMPC
 
 EINVAL = -1  # SRBD_QP_EINVAL
-# NMPC_solver.cpp:70-82, as tests/test_gpu_nmpc.py
-NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
-            tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
-            split_step=1)
 
 
 def test_set_robots_is_exported_and_rejects_a_null_handle(pkg):
@@ -94,16 +91,15 @@ def test_identical_robots_give_the_bits_of_the_shared_closed_loop(pkg, oracle, a
     p = dataclasses.replace(sm.SrbdParams(), mass=13.0, mu=0.6)
     xs, us, x, alpha, plan = RH.walking_case(sm, p, B, N, T, 5)
     wrench = np.random.default_rng(6).uniform(-15.0, 15.0, size=(B, T, 6))
-    want = RH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, 15, "none", wrench=wrench,
-                          substeps=2, alpha_reset=alpha_reset)
-    got = BH.closed_loop(sm, oracle, [p] * B, [p] * B, plan, xs, us, x, alpha, T, NMPC, 15, "none",
-                         wrench=wrench, substeps=2, alpha_reset=alpha_reset)
+    loop = lambda **params: RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, 15, "none", plan=plan, wrench=wrench,
+                                           substeps=2, alpha_reset=alpha_reset, **params)
+    want = loop(p=p)
+    got = loop(model=[p] * B, plant=[p] * B)
     for k in ("x_log", "u_log", "sqp_iter", "converged", "xs", "us", "x", "alpha"):
         assert np.array_equal(got[k], want[k]), k
     assert got["margin"] == want["margin"]
     # and the plant list is what moves the plant: a heavier true robot ends elsewhere
     heavy = [dataclasses.replace(p, mass=1.2 * p.mass)] * B
-    other = BH.closed_loop(sm, oracle, [p] * B, heavy, plan, xs, us, x, alpha, T, NMPC, 15, "none",
-                           wrench=wrench, substeps=2, alpha_reset=alpha_reset)
+    other = loop(model=[p] * B, plant=heavy)
     assert np.array_equal(other["u_log"][:, 0], want["u_log"][:, 0])  # the first step saw the same x
     assert not np.array_equal(other["x_log"][:, 1], want["x_log"][:, 1])

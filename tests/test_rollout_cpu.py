@@ -1,22 +1,22 @@
 """The closed loop (srbd_qp_srbd_advance_f64 / srbd_qp_srbd_rollout_f64) without a GPU: the two
 entry points exist and validate, the host model's plant_step and shift_guess are the operations
-include/srbd_qp.h states, and the host closed loop of tests/rollout_host.py is the host SQP
-loop when it runs one tick."""
+include/srbd_qp.h states, the host closed loop of tests/rollout_host.py is the host SQP loop
+when it runs one tick, and with every feature on its tick 0 is the primitives in order."""
 import ctypes as C
 import subprocess
 
 import numpy as np
 import pytest
 
+import contact_host as CH
 import nmpc_plan_host as PH
+import robots_host as BH
 import rollout_host as RH
+import terrain_host as TH
+from srbd_device import NMPC
 
 ROLLOUT_SYMBOLS = ("srbd_qp_srbd_advance_f64", "srbd_qp_srbd_rollout_f64")
 EINVAL = -1  # SRBD_QP_EINVAL
-# NMPC_solver.cpp:70-82, as tests/test_gpu_nmpc.py
-NMPC = dict(mode="Speed", iter_max=30, alpha_min=1e-8, mu0=1e2, tol_stat=1e-4, tol_eq=1e-4,
-            tol_ineq=1e-4, tol_comp=1e-4, reg_prim=1e-12, warm_start=0, pred_corr=1, ric_alg=0,
-            split_step=1)
 
 
 def random_feet(p, B, seed):
@@ -150,7 +150,7 @@ def test_one_tick_of_the_host_loop_is_the_host_sqp_loop(pkg, oracle, alpha_reset
     B, N, T = 2, 6, 1
     p = sm.SrbdParams()
     xs, us, x, alpha, plan = RH.walking_case(sm, p, B, N, T, 5)
-    out = RH.closed_loop(sm, oracle, p, plan, xs, us, x, alpha, T, NMPC, 15, "none",
+    out = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, 15, "none", p=p, plan=plan,
                          alpha_reset=alpha_reset)
     w = RH.window(sm, plan, 0, N)
     assert w.x_ref.shape == (B, N + 1, 12) and w.foot_r.shape == (B, N, 3) and w.fz_max.shape == (B, N, 2)
@@ -170,3 +170,63 @@ def test_one_tick_of_the_host_loop_is_the_host_sqp_loop(pkg, oracle, alpha_reset
     assert np.array_equal(out["x_log"][:, 1], sm.plant_step(x, hus[:, 0], p, w.foot_r[:, 0], w.foot_l[:, 0]))
     sx, su = sm.shift_guess(hxs, hus, p, w)
     assert np.array_equal(out["xs"], sx) and np.array_equal(out["us"], su)
+
+
+def test_tick_0_of_the_combined_loop_is_the_primitives_in_order(pkg, oracle):
+    """A gait on terrain, a contact with that terrain as the true ground and per-robot plants,
+    all at once: tick 0 is gait_plan(terrain=), the host SQP loop per robot, contact_flags,
+    plant_step(contact=) per robot and shift_guess, called directly in that order."""
+    sm = pkg.srbd_model
+    B, N, T = 2, 6, 2
+    p = sm.SrbdParams()
+    xs, us, x, alpha, gait, cmd, ref_pose, foot_now = TH.stairs_case(sm, p, B, N, T, 5)
+    ter = TH.stairs_terrain(sm)
+    contact = sm.SrbdContact(mu=0.3, fz_hi=400.0, fz_contact=0.5 * (gait.fz_swing + gait.fz_stance),
+                             ground_z=gait.ground_z, ground=ter, z_min=0.3, cos_tilt_min=0.5)
+    model = [p] * B
+    plant = BH.draw_plant(model, 6)
+    out = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, 15, "none", model=model, plant=plant, gait=gait,
+                         cmd=cmd, ref_pose=ref_pose, foot_now=foot_now, tick0=4, terrain=ter, contact=contact,
+                         state=CH.zero_state(B))
+    assert set(out) >= {"foot_log", "windows", "q_log", "poses", "state", "fallen_log", "values"}
+    # 1. the window
+    w, pose, feet = sm.gait_plan(p, gait, cmd[:, 0], x, 4, ref_pose, foot_now, N, terrain=ter)
+    for k in RH.FIELDS:
+        assert np.array_equal(getattr(out["windows"][0], k), getattr(w, k)), k
+    assert np.array_equal(out["poses"][0], pose) and np.array_equal(out["feet"][0], feet)
+    assert np.array_equal(out["foot_log"][:, 0], feet) and np.array_equal(out["fz_log"][:, 0], w.fz_max[:, 0])
+    # 2. the SQP loop per robot
+    res = [PH.sqp_loop(sm, oracle, model[i], w.robot(i), xs[i], us[i], x[i], float(alpha[i]), NMPC, 15, "none")
+           for i in range(B)]
+    for i, (hx, hu, ha, hit, hcv, hm) in enumerate(res):
+        sx, su, sa, sit, scv, smg = out["steps"][0][i]
+        assert np.array_equal(sx, hx) and np.array_equal(su, hu)
+        assert (sa, sit, scv, smg) == (ha, hit, hcv, hm)
+        assert out["sqp_iter"][i, 0] == hit and bool(out["converged"][i, 0]) == hcv
+    hxs, hus = np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
+    # 3. the contact flags, 4. the plant step per robot with the true robot's parameters
+    on = sm.contact_flags(contact, w.fz_max[:, 0], B)
+    assert not on.all() and on.any()  # a swing foot and a stance foot at tick 0
+    state = CH.zero_state(B)
+    for i in range(B):
+        x1, ua, st = sm.plant_step(x[i:i + 1], hus[i:i + 1, 0], plant[i], w.foot_r[i:i + 1, 0], w.foot_l[i:i + 1, 0],
+                                   contact=RH.robot_contact(contact, i), in_contact=on[i:i + 1],
+                                   state={k: v[i:i + 1] for k, v in state.items()})
+        assert np.array_equal(out["x_log"][i, 1], x1[0]) and np.array_equal(out["u_log"][i, 0], ua[0])
+        assert not np.array_equal(ua[0], hus[i, 0])  # the applied input is the projected one
+        for k in state:
+            state[k][i] = st[k][0]
+    assert np.array_equal(out["fallen_log"][:, 0], state["fallen"])
+    for got, want in zip(out["values"][0], sm.fall_values(out["x_log"][:, 1], contact)):
+        assert np.array_equal(got, want)
+    # 5. the shift, with the model's parameters, after which tick 1 starts
+    parts = [sm.shift_guess(hxs[i:i + 1], hus[i:i + 1], model[i], sm.SrbdPlan(*[getattr(w, k)[i:i + 1] for k in RH.FIELDS]))
+             for i in range(B)]
+    # (tick 1's SQP loop starts from the shifted guess: its result pins the shift)
+    w1 =sm.gait_plan(p, gait, cmd[:, 1], out["x_log"][:, 1], 5, pose, feet, N, terrain=ter)[0]
+    for k in RH.FIELDS:
+        assert np.array_equal(getattr(out["windows"][1], k), getattr(w1, k)), k
+    for i in range(B):
+        r = PH.sqp_loop(sm, oracle, model[i], w1.robot(i), parts[i][0][0], parts[i][1][0], out["x_log"][i, 1],
+                        out["steps"][0][i][2], NMPC, 15, "none")
+        assert np.array_equal(out["steps"][1][i][0], r[0]) and np.array_equal(out["steps"][1][i][1], r[1])

@@ -4,7 +4,8 @@ properties include/srbd_qp.h states.  No terrain and flat ground are the planner
 plane is sampled exactly and moves no foothold; the sampler is exact on nodes, extends its edges
 and is continuous; on stairs the selection leaves the risers, never for a worse cost, and breaks
 ties towards the smallest candidate index; a stance foot keeps its bits; and one tick of
-tests/terrain_host.py's loop is gait_plan(terrain=...) followed by the host SQP loop."""
+tests/rollout_host.py's loop with the terrain is gait_plan(terrain=...) followed by the host SQP
+loop."""
 import subprocess
 
 import numpy as np
@@ -12,8 +13,10 @@ import pytest
 
 import gait_host as GH
 import nmpc_plan_host as PH
+import rollout_host as RH
 import terrain_host as TH
-from test_gait_cpu import FIELDS, NMPC, rot
+from gait_host import rot
+from srbd_device import FIELDS, NMPC
 
 TERRAIN_SYMBOLS = ("srbd_qp_srbd_set_terrain_f64", "srbd_qp_srbd_terrain_height_f64")
 # the two map shapes of the tests, neither square: (ny, nx, x0, y0, cell) around the robots' start
@@ -212,8 +215,8 @@ def test_one_tick_of_the_host_terrain_loop_is_gait_plan_then_the_host_sqp_loop(p
     p = sm.SrbdParams()
     xs, us, x, alpha, gait, cmd, ref_pose, foot_now = TH.stairs_case(sm, p, B, N, T, 5)
     ter = TH.stairs_terrain(sm)
-    out = TH.closed_loop(sm, oracle, p, gait, ter, cmd, xs, us, x, alpha, ref_pose, foot_now, T, NMPC, 15, "none",
-                         tick0=4)
+    out = RH.closed_loop(sm, oracle, xs, us, x, alpha, T, NMPC, 15, "none", p=p, gait=gait, cmd=cmd,
+                         ref_pose=ref_pose, foot_now=foot_now, tick0=4, terrain=ter)
     w, pose, feet = sm.gait_plan(p, gait, cmd[:, 0], x, 4, ref_pose, foot_now, N, terrain=ter)
     flat = sm.gait_plan(p, gait, cmd[:, 0], x, 4, ref_pose, foot_now, N)[0]
     assert not np.array_equal(w.foot_r, flat.foot_r) or not np.array_equal(w.foot_l, flat.foot_l)
