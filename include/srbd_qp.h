@@ -40,6 +40,10 @@
  *   srbd_qp_srbd_set_terrain_f64 height maps under the gait planner: foothold height, reference
  *                                body height and foothold selection; srbd_qp_srbd_terrain_height_f64
  *                                samples them.
+ *   srbd_qp_srbd_set_contact_f64 the plant's contact model and fall detection.
+ *   srbd_qp_srbd_set_active_f64  which robots a step steps (a mask, not the fallen ones), and its
+ *                                SQP iterations over the robots that still iterate only;
+ *                                srbd_qp_srbd_step_work counts the QPs that were solved.
  *
  * ------------------------------------------------------------------------
  * Problem (per QP, stages k = 0..N), identical to hpipm::OcpQp
@@ -812,9 +816,9 @@ int srbd_qp_srbd_terrain_height_f64(srbd_qp_handle h, int n, const double* xy /*
  * without nx = nu = 12 is SRBD_QP_EDIM.  ground.search / ground.w_rough are ignored.
  * Caller's contract (device data, not checked): mu_r finite and >= 0, map indices in range.
  * Out of scope: feet that slide when friction saturates (the foot stays where the plan put it);
- * any body-ground collision; skipping the NMPC step of fallen robots (they are still stepped,
- * their plant is frozen); re-arming a fallen robot inside a rollout (the caller resets x and
- * fallen between rollouts); srbd_qp_multi_*, the hpipm-cpp shim, fp32.
+ * any body-ground collision; re-arming a fallen robot inside a rollout (the caller resets x and
+ * fallen between rollouts); srbd_qp_multi_*, the hpipm-cpp shim, fp32.  (Whether the NMPC step
+ * still runs for a fallen robot is srbd_active_f64.skip_fallen's choice, below.)
  * ---------------------------------------------------------------------- */
 typedef struct srbd_contact_f64 {
   double mu;              /* plant friction coefficient of every robot where mu_r is NULL      */
@@ -833,6 +837,67 @@ typedef struct srbd_contact_f64 {
   unsigned* sat;          /* device [batch] in/out, optional: OR of the limits that were active */
 } srbd_contact_f64;
 int srbd_qp_srbd_set_contact_f64(srbd_qp_handle h, const srbd_contact_f64* contact);
+
+/* ------------------------------------------------------------------------
+ * Active sets (additive to ABI 12): which robots of the batch an NMPC step steps, and whether
+ * its SQP iterations are launched over the robots that still iterate only.  Without one, every
+ * SQP iteration linearises and solves the whole batch until the slowest robot has converged: a
+ * step costs (largest sqp_iter) x batch QP solves where sum_i sqp_iter[i] are needed.
+ * The call attaches to the handle like set_robots / set_terrain / set_contact: it copies the
+ * struct and does no device work; active == NULL, or a struct with mask == NULL, skip_fallen == 0
+ * and compact == 0, clears it, and with it cleared every call launches the kernels it launched
+ * before and gives the same bits.  It is read by the NMPC step only: srbd_qp_srbd_nmpc_f64,
+ * srbd_qp_srbd_nmpc_plan_f64 and so both rollouts.  The advance, the planner, the plain
+ * linearisation and line search and the solves do not read it.  mask is device memory with at
+ * least `batch` rows, read when the step starts: keep it alive until the step has returned.
+ *
+ * Robot i is active in a step iff, when the step starts, (mask == NULL or mask[i] != 0) and
+ * (skip_fallen == 0 or contact.fallen[i] == 0), contact the handle's srbd_contact_f64.  This is
+ * the only place where the controller reads anything of the contact model, and it reads fallen
+ * only.  A robot that is not active: xs, us and alpha keep their bits, sqp_iter[i] = 0 and
+ * converged[i] = 0.  In a rollout the advance runs for it as always (the shift happens; a fallen
+ * robot's plant is frozen) and the logs hold those zeros for that tick.
+ *
+ * compact == 0: the kernels and launch shapes of a step without an active set; a robot that is
+ * not active rides along as a robot does whose loop has stopped.  An active robot gets the bits
+ * it gets without an active set.
+ * compact == 1: SQP iteration `it` builds the QPs of the n_it robots still iterating as a dense
+ * batch of n_it, in ascending robot order, solves that batch with srbd_qp_solve_f64 and
+ * line-searches those robots; with n_0 == 0 the call returns after the selection.  A robot's
+ * result is what the solve gives its QP in a batch of n_it: bit-identical to compact == 0 wherever
+ * the solve's kernel choice is the same for n_it and for `batch`.  That holds for
+ * SRBD_QP_SRBD_NONE at any size: the step solves the n_it QPs with the Riccati kernel the whole
+ * batch takes (the streaming kernel also for the few QPs left of a batch of more than 256, where
+ * srbd_qp_solve_f64 on its own would take the single-QP kernels, which sum in another order),
+ * and a Riccati solve of a subset has the full batch's bits.  For BOX_U and CONE it holds while
+ * n_it and `batch` lie on the same side of the latency IPM's limit (512 QPs).  Across that
+ * limit the stragglers are solved by the latency IPM, the faster kernel for few QPs, and the two
+ * settings agree to the solver's tolerance, not to the bit.
+ * The step costs one more 4-byte read-back (the count of active robots) when an active set is
+ * attached, and two index lists of `capacity` ints in its scratch.
+ *
+ * Checks.  At set time: a NULL handle, skip_fallen or compact not 0 or 1: SRBD_QP_EINVAL; a
+ * handle without nx = nu = 12: SRBD_QP_EDIM.  At the step or rollout, before any device work
+ * (every array is left as it was): skip_fallen without a contact on the handle, or with a contact
+ * whose fallen is NULL: SRBD_QP_EINVAL; compact == 1 with settings->warm_start != 0:
+ * SRBD_QP_EINVAL (the warm start reads the previous iterate at the QP's position, which under
+ * compaction belongs to another robot).
+ * Out of scope: compaction with an IPM warm start; a step without read-backs; skipping the
+ * planner or the advance of a robot that is not active; srbd_qp_multi_*, the hpipm-cpp shim, fp32.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_active_f64 {
+  const int* mask;   /* device [batch], optional: robot i is stepped iff mask[i] != 0; NULL = all  */
+  int skip_fallen;   /* 1: a robot with contact.fallen[i] != 0 when the step starts is not stepped */
+  int compact;       /* 0: full-batch launches (a robot that is not stepped rides along);
+                        1: every SQP iteration is launched over the robots still iterating only   */
+} srbd_active_f64;
+int srbd_qp_srbd_set_active_f64(srbd_qp_handle h, const srbd_active_f64* active);
+/* The work of the last NMPC step on this handle (of a rollout: summed over its ticks), host
+ * counters that are always kept: *sqp_iterations the SQP loop iterations that ran, *qp_solves the
+ * sum over them of the batch size passed to the solve -- iterations x batch without compaction,
+ * and exactly sum_i sqp_iter[i] with compact == 1.  Either pointer may be NULL; a NULL handle is
+ * SRBD_QP_EINVAL. */
+int srbd_qp_srbd_step_work(srbd_qp_handle h, long long* qp_solves, long long* sqp_iterations);
 
 /* ------------------------------------------------------------------------
  * One solver over several devices, driven from one host thread (SURVEY.md 5,

@@ -306,6 +306,34 @@ class Contact:
         return cs
 
 
+class ActiveStruct(C.Structure):
+    """srbd_active_f64."""
+    _fields_ = [("mask", _dp), ("skip_fallen", C.c_int), ("compact", C.c_int)]
+
+
+class Active:
+    """Which robots the NMPC step steps, for Handle.set_active (srbd_active_f64; include/srbd_qp.h
+    states what a robot that is not stepped keeps).  mask: an int32 device tensor [B], robot i is
+    stepped iff mask[i] != 0 (None: all); skip_fallen: a robot whose contact.fallen is set when the
+    step starts is not stepped (needs a Contact with fallen on the handle); compact: every SQP
+    iteration is launched over the robots that still iterate only (needs warm_start = 0).  Dtype,
+    contiguity, shape and device are checked here, with ValueError.  The holder keeps the tensor
+    alive."""
+
+    def __init__(self, mask=None, skip_fallen=False, compact=False):
+        self.mask, self.skip_fallen, self.compact = mask, skip_fallen, compact
+        self.rows = None
+
+    def struct(self, device=None) -> ActiveStruct:
+        import torch
+        self.rows = None
+        if self.mask is not None:
+            _check_tensor("active.mask", self.mask, (torch.int32,), ("B",), device, "the handle", any_gpu=True,
+                          expected="(B,)")
+            self.rows = int(self.mask.shape[0])
+        return ActiveStruct(_tensor_ptr(self.mask) or None, int(self.skip_fallen), int(self.compact))
+
+
 class AdvanceStruct(C.Structure):
     """srbd_advance_f64."""
     _fields_ = [("substeps", C.c_int), ("wrench", _dp)]
@@ -421,6 +449,8 @@ def _prototypes():
         "srbd_qp_srbd_set_terrain_f64": (i, [h, P(TerrainStruct)], maybe),
         "srbd_qp_srbd_terrain_height_f64": (i, [h, i] + [vp] * 4, maybe),
         "srbd_qp_srbd_set_contact_f64": (i, [h, P(ContactStruct)], maybe),
+        "srbd_qp_srbd_set_active_f64": (i, [h, P(ActiveStruct)], maybe),  # active sets
+        "srbd_qp_srbd_step_work": (i, [h, P(C.c_longlong), P(C.c_longlong)], maybe),
         "srbd_qp_srbd_gait_plan_f64": (i, [h, i, mp, P(GaitStruct), vp, vp, C.c_longlong] + [vp] * 7, maybe),
         "srbd_qp_srbd_rollout_gait_f64": (i, [h, i, mp, P(GaitStruct), P(RolloutGaitStruct), ls, st, i, i,
                                               P(RolloutStruct)] + [vp] * 4, maybe),
@@ -612,6 +642,27 @@ class Handle:
               "srbd_qp_srbd_set_contact_f64")
         self._contact = contact
 
+    def set_active(self, active: Optional["Active"] = None) -> None:
+        """srbd_qp_srbd_set_active_f64: srbd_nmpc, srbd_rollout and srbd_rollout_gait on this handle
+        afterwards step the Active's robots only: a robot that is not stepped keeps the bits of
+        xs, us and alpha and reports sqp_iter = converged = 0; with compact, every SQP iteration
+        is launched over the robots that still iterate.  None (or an Active of defaults) clears
+        it: the step as it was, bit for bit.  The handle keeps the Active, and so its mask, alive
+        until it is replaced."""
+        import torch
+        a = None if active is None else active.struct(torch.device("cuda", self.device))
+        check(lib().srbd_qp_srbd_set_active_f64(self._h, None if a is None else C.byref(a)),
+              "srbd_qp_srbd_set_active_f64")
+        self._active = active
+
+    def step_work(self):
+        """srbd_qp_srbd_step_work: (qp_solves, sqp_iterations) of the last srbd_nmpc on this handle,
+        or of the last rollout summed over its ticks: the QPs passed to the solver and the SQP
+        loop iterations that ran.  With Active(compact=True) qp_solves is sqp_iter.sum()."""
+        q, n = C.c_longlong(0), C.c_longlong(0)
+        check(lib().srbd_qp_srbd_step_work(self._h, C.byref(q), C.byref(n)), "srbd_qp_srbd_step_work")
+        return int(q.value), int(n.value)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().srbd_qp_destroy(self._h)
@@ -786,13 +837,17 @@ def model_params(p) -> ModelParams:
 
 
 _TOO_FEW_ROWS = {"robots": "the handle's robots have {} rows", "terrain": "the handle's terrain has a map_r of {} rows",
-                 "contact": "the handle's contact has tensors of {} rows"}
+                 "contact": "the handle's contact has tensors of {} rows",
+                 "active": "the handle's active set has a mask of {} rows"}
 
 
 def _check_rows(handle, B, *holders) -> None:
     """The call reads (a contact: also writes) rows 0..B-1 of what the handle holds from
-    Handle.set_robots / set_terrain / set_contact, those named in `holders`: ValueError if one has
-    fewer rows."""
+    Handle.set_robots / set_terrain / set_contact / set_active, those named in `holders`:
+    ValueError if one has fewer rows.  An active set with skip_fallen reads the contact's."""
+    act = getattr(handle, "_active", None)
+    if "active" in holders and "contact" not in holders and act is not None and act.skip_fallen:
+        holders += ("contact",)
     for kind in holders:
         held = getattr(handle, "_" + kind, None)
         for one in held if isinstance(held, tuple) else (held,):
@@ -882,7 +937,7 @@ def srbd_nmpc(handle: Handle, xs, us, x0, alpha, constraints: str = "none",
     import torch
     B = xs.shape[0]
     plan_ref = _plan_ref(plan, B, us.shape[1], xs.device)
-    _check_rows(handle, B, "robots")
+    _check_rows(handle, B, "robots", "active")
     it = torch.zeros(B, dtype=torch.int32, device=xs.device)
     conv = torch.zeros(B, dtype=torch.int32, device=xs.device)
     p = params or default_model_params()
@@ -973,7 +1028,7 @@ def srbd_rollout(handle: Handle, xs, us, x, alpha, ticks: int, constraints: str 
         _check_f64("wrench", wrench, (B, max(T, 0), 6), dev)
     P = N + T - 1 if plan_stages is None else int(plan_stages)
     plan_ref = _plan_ref(plan, B, P, dev)
-    _check_rows(handle, B, "robots", "contact")
+    _check_rows(handle, B, "robots", "contact", "active")
     logs, roll = _rollout_logs(B, T, P, dev, wrench, substeps, alpha_reset)
     p = params or default_model_params()
     lp = ls or default_linesearch()
@@ -1054,7 +1109,7 @@ def srbd_rollout_gait(handle: Handle, gait: Gait, cmd, xs, us, x, alpha, ref_pos
     if wrench is not None:
         _check_f64("wrench", wrench, (B, rows, 6), dev)
     gs = gait.struct(B, dev)
-    _check_rows(handle, B, "robots", "terrain", "contact")
+    _check_rows(handle, B, "robots", "terrain", "contact", "active")
     logs, roll = _rollout_logs(B, T, 0, dev, wrench, substeps, alpha_reset)
     foot_log = torch.zeros(B, rows, 2, 3, dtype=torch.float64, device=dev)
     fz_log = torch.zeros(B, rows, 2, dtype=torch.float64, device=dev)

@@ -80,6 +80,12 @@ struct srbd_qp_handle_s {
   // caller's struct; has_contact false: none)
   srbd_contact_f64 contact{};
   bool has_contact = false;
+  // srbd_qp_srbd_set_active_f64: which robots the NMPC step steps (a copy of the caller's
+  // struct; has_active false: all of them, the launches of a handle that never had one)
+  srbd_active_f64 active{};
+  bool has_active = false;
+  // srbd_qp_srbd_step_work: the work of the last NMPC step, or of a rollout's steps
+  long long work_qp_solves = 0, work_sqp_iterations = 0;
   // settings.f64_rescue: the compact fp64 batch, and that of the cold fp64 re-solve of
   // rescued QPs the continuation left unsolved
   srbd::Buffer resc, resc2;
@@ -104,6 +110,9 @@ struct srbd_qp_handle_s {
   int* lat_flag_host = nullptr;
   int* lqsw_idx = nullptr;
   bool force_batched = false;
+  // the compacted NMPC step of a batch above the single-QP kernels' limit: its sub-batches are
+  // solved by the streaming Riccati kernel too, whatever their size (set around those solves)
+  bool riccati_streaming = false;
   // live-QP control of the IPM launch sequence (ProblemArgsT::ctl): device counters and
   // control words, decided on the device (the host never waits on them)
   int* ctl = nullptr;

@@ -195,12 +195,13 @@ static int solve_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, c
   } else {
     // (the single-QP kernel computes the residuals itself when the problem is not embedded)
     run.fuse_res = st->compute_residuals && !padded;
-    e = srbd::launch_riccati_unconstr(run, strm);
+    e = srbd::launch_riccati_unconstr(run, strm, h->riccati_streaming);
     if (e == hipSuccess && padded) e = srbd::unpad_solution<T>(a, run, strm);
     // residual norms / objective of the solution when asked for (HPIPM computes them
     // for nc = 0 too; an extra pass over the QP data, so only on request); the stat
     // table's row 0 gets them as well
-    if (e == hipSuccess && (s->res || s->obj || s->stat) && !srbd::unconstr_fused_residuals(run)) {
+    if (e == hipSuccess && (s->res || s->obj || s->stat) &&
+        (h->riccati_streaming || !srbd::unconstr_fused_residuals(run))) {
       if (st->compute_residuals) {
         e = srbd::launch_unconstr_residuals<T>(a, strm);
       } else {

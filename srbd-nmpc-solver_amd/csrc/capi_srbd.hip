@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <utility>
 
 using namespace srbd::capi;
 
@@ -145,6 +146,24 @@ int srbd_qp_srbd_set_contact_f64(srbd_qp_handle h, const srbd_contact_f64* conta
   return SRBD_QP_OK;
 }
 
+int srbd_qp_srbd_set_active_f64(srbd_qp_handle h, const srbd_active_f64* active) {
+  if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
+  if (h->dims.nx != 12 || h->dims.nu != 12) return fail(SRBD_QP_EDIM, "an SRBD active set needs nx = nu = 12");
+  const srbd_active_f64 a = active ? *active : srbd_active_f64{};
+  if ((a.skip_fallen != 0 && a.skip_fallen != 1) || (a.compact != 0 && a.compact != 1))
+    return fail(SRBD_QP_EINVAL, "set_active: skip_fallen and compact must be 0 or 1");
+  h->active = a;
+  h->has_active = a.mask || a.skip_fallen || a.compact;
+  return SRBD_QP_OK;
+}
+
+int srbd_qp_srbd_step_work(srbd_qp_handle h, long long* qp_solves, long long* sqp_iterations) {
+  if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
+  if (qp_solves) *qp_solves = h->work_qp_solves;
+  if (sqp_iterations) *sqp_iterations = h->work_sqp_iterations;
+  return SRBD_QP_OK;
+}
+
 // The _plan_ entry points hold the checks and the work; the plain ones forward a NULL plan.
 // All of them read the handle's robots (srbd_qp_srbd_set_robots_f64).
 int srbd_qp_srbd_linearize_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
@@ -213,11 +232,15 @@ int srbd_qp_srbd_linesearch_f64(srbd_qp_handle h, int batch, const srbd_model_pa
                                           converged, stream);
 }
 
-int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
-                               const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
-                               const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
-                               double* xs, double* us, const double* x0, double* alpha,
-                               int* sqp_iter, int* converged) {
+}  // extern "C"
+
+namespace {
+// The NMPC step (srbd_qp_srbd_nmpc_plan_f64).  add_work: a rollout's tick, whose work is added
+// to the handle's counters (srbd_qp_srbd_step_work); a step of its own starts them at zero.
+int nmpc_step(srbd_qp_handle h, int batch, const srbd_model_params* params, const srbd_plan_f64* plan,
+              const srbd_linesearch_params* ls, const srbd_qp_settings* settings, int constraints,
+              int sqp_max_loop, double* xs, double* us, const double* x0, double* alpha, int* sqp_iter,
+              int* converged, bool add_work) {
   if (!h || !params || !ls || !settings || !xs || !us || !x0 || !alpha || !sqp_iter || !converged)
     return fail(SRBD_QP_EINVAL, "NULL argument");
   const srbd_qp_dims& d = h->dims;
@@ -231,6 +254,13 @@ int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_par
     return fail(SRBD_QP_EINVAL, "the handle's dims do not match the constraints mode");
   rc = srbd_qp_check_settings(settings);
   if (rc) return rc;
+  // the active set (srbd_qp_srbd_set_active_f64): act false is the step without one
+  const bool act = h->has_active, compact = act && h->active.compact;
+  if (act && h->active.skip_fallen && !(h->has_contact && h->contact.fallen))
+    return fail(SRBD_QP_EINVAL, "active set: skip_fallen needs a contact with fallen on the handle");
+  if (compact && settings->warm_start != 0)
+    return fail(SRBD_QP_EINVAL, "active set: compact does not go with settings.warm_start");
+  if (!add_work) h->work_qp_solves = h->work_sqp_iterations = 0;
   if (batch == 0 || sqp_max_loop == 0) return SRBD_QP_OK;
   srbd::DeviceGuard guard(h->device);
   hipStream_t strm = h->stream;
@@ -249,6 +279,7 @@ int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_par
   const Buf bx0 = take(B * 12), bx = take(B * (N + 1) * 12), bu = take(B * N * 12),
             bpi = take(B * (N + 1) * 12);
   const Buf bint = take(B * 4 + 8);  // conv, done, status, iter (ints) + active
+  const Buf bidx = take(act ? B : 0);  // an active set's two lists of B ints
   hipError_t e = h->nmpc.reserve(top * sizeof(double));
   if (e == hipSuccess && !h->nmpc_active_host)
     e = hipHostMalloc(reinterpret_cast<void**>(&h->nmpc_active_host), sizeof(int));
@@ -266,26 +297,66 @@ int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_par
   srbd_qp_solution_f64 sol{};
   sol.x = at(bx); sol.u = at(bu); sol.pi = at(bpi); sol.status = status; sol.iter = iters;
   const srbd_model_params p = with_qf_scale(params, d.N);
+  // the count of robots still iterating, through the 4-byte read-back
+  auto read_active = [&]() {
+    hipError_t r = hipMemcpyAsync(h->nmpc_active_host, active, sizeof(int), hipMemcpyDeviceToHost, strm);
+    return r == hipSuccess ? hipStreamSynchronize(strm) : r;
+  };
+  // With an active set the first list says who is stepped (and writes every robot's loop state);
+  // n: the QPs of an iteration, cur / next: its robots and the next one's (compact only).
+  int n = batch;
+  int *cur = reinterpret_cast<int*>(at(bidx)), *next = cur ? cur + B : nullptr;
+  if (act) {
+    e = srbd::launch_nmpc_select_first(batch, h->active.mask, h->active.skip_fallen ? h->contact.fallen : nullptr,
+                                       done, sqp_iter, converged, cur, active, strm);
+    if (e == hipSuccess) e = read_active();
+    if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "NMPC loop: ", e);
+    if (*h->nmpc_active_host == 0) return SRBD_QP_OK;  // nobody is stepped
+    if (compact) n = *h->nmpc_active_host;
+  }
   // NMPC_solver.cpp:362-372: prepareQpStructures; solveQpProblems; if (checkConvergence()) break;
   for (int it = 0; it < sqp_max_loop && e == hipSuccess; ++it) {
-    e = srbd::launch_srbd_linearize(p, batch, d.N, constraints, xs, us, qd, strm, plan, &h->robots_model);
+    const int* idx = compact ? cur : nullptr;  // QP j is robot idx[j]; NULL: robot j
+    e = srbd::launch_srbd_linearize(p, n, d.N, constraints, xs, us, qd, strm, plan, &h->robots_model, idx);
     if (e == hipSuccess)
-      e = srbd::launch_nmpc_prep(batch, d.N, it, xs, x0, at(bx0), done, sqp_iter, converged, strm);
+      e = srbd::launch_nmpc_prep(n, d.N, !act && it == 0, xs, x0, at(bx0), done, sqp_iter, converged, strm, idx);
     if (e != hipSuccess) break;
-    rc = srbd_qp_solve_f64(h, batch, settings, &qd, &sol, strm);
+    // A compacted unconstrained iteration is solved by the kernel the whole batch takes: the
+    // streaming Riccati kernel also for the few QPs left of a batch above the single-QP kernels'
+    // limit.  A robot then has the bits of the step without compaction, at any batch size.
+    h->riccati_streaming = compact && !box && !cone && batch > srbd::riccati_single_qp_batch_max();
+    rc = srbd_qp_solve_f64(h, n, settings, &qd, &sol, strm);
+    h->riccati_streaming = false;
     if (rc) return rc;
-    e = srbd::launch_srbd_linesearch(p, *ls, batch, d.N, xs, us, at(bx), at(bu), alpha, nullptr,
-                                     conv, strm, done, plan, &h->robots_model);
+    h->work_qp_solves += n;
+    h->work_sqp_iterations += 1;
+    e = srbd::launch_srbd_linesearch(p, *ls, n, d.N, xs, us, at(bx), at(bu), alpha, nullptr,
+                                     conv, strm, done, plan, &h->robots_model, idx);
     if (e == hipSuccess)
-      e = srbd::launch_nmpc_after(batch, it, conv, done, sqp_iter, converged, active, strm);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(h->nmpc_active_host, active, sizeof(int), hipMemcpyDeviceToHost, strm);
-    if (e == hipSuccess) e = hipStreamSynchronize(strm);
+      e = compact ? srbd::launch_nmpc_select_next(n, it, cur, conv, done, sqp_iter, converged, next, active, strm)
+                  : srbd::launch_nmpc_after(batch, it, conv, done, sqp_iter, converged, active, strm);
+    if (e == hipSuccess) e = read_active();
     if (e == hipSuccess && *h->nmpc_active_host == 0) break;  // every robot has converged
+    if (e == hipSuccess && compact) {
+      n = *h->nmpc_active_host;
+      std::swap(cur, next);
+    }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(strm);
   if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "NMPC loop: ", e);
   return SRBD_QP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int srbd_qp_srbd_nmpc_plan_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                               const srbd_plan_f64* plan, const srbd_linesearch_params* ls,
+                               const srbd_qp_settings* settings, int constraints, int sqp_max_loop,
+                               double* xs, double* us, const double* x0, double* alpha,
+                               int* sqp_iter, int* converged) {
+  return nmpc_step(h, batch, params, plan, ls, settings, constraints, sqp_max_loop, xs, us, x0, alpha, sqp_iter,
+                   converged, false);
 }
 int srbd_qp_srbd_nmpc_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
                           const srbd_linesearch_params* ls, const srbd_qp_settings* settings,
@@ -523,8 +594,8 @@ static int rollout_impl(srbd_qp_handle h, int batch, const srbd_model_params* pa
     e = srbd::launch_rollout_rows(batch, rt, w.nrows, roll->alpha_reset > 0.0 ? alpha : nullptr,
                                   roll->alpha_reset, strm);
     if (e != hipSuccess) return hip_fail(alloc_code(e), "rollout: ", e);
-    rc = srbd_qp_srbd_nmpc_plan_f64(h, batch, params, wplan, ls, settings, constraints, sqp_max_loop, xs, us, x,
-                                    alpha, it_step, cv_step);
+    rc = nmpc_step(h, batch, params, wplan, ls, settings, constraints, sqp_max_loop, xs, us, x, alpha, it_step,
+                   cv_step, true);
     if (rc) return rc;
     // the plant step, with column t of the logs (x_log's columns are one ahead: column 0 is the start)
     srbd::AdvanceIo io = advance_io(roll->substeps, xs, us, x, roll->wrench, roll->u_log, t, T);

@@ -174,7 +174,10 @@ hipError_t launch_ipm_box_batched(const ProblemArgsT<double>& a, hipStream_t str
 size_t ws_doubles_unconstr(int N);
 
 template <typename T>
-hipError_t launch_riccati_unconstr(const ProblemArgsT<T>& a, hipStream_t stream);
+hipError_t launch_riccati_unconstr(const ProblemArgsT<T>& a, hipStream_t stream, bool streaming = false);
+// batches above this take the streaming kernel; `streaming` makes smaller ones take it too (a
+// QP's bits are then those it has in a large batch; the residuals are not fused)
+int riccati_single_qp_batch_max();
 // per-device launch attributes of the unconstrained kernels, on the current device
 // (srbd_qp_create, after selecting the handle's device)
 hipError_t prepare_riccati_device();
@@ -233,22 +236,32 @@ hipError_t unpad_slack(const ProblemArgsT<double>& a, const SoftArgsT<double>& s
 }  // namespace srbd
 #include "../../include/srbd_qp.h"
 namespace srbd {
+// idx (optional, the NMPC step's compaction): QP j of the launch belongs to robot idx[j] -- per-robot
+// rows (xs, us, x0, alpha, merit, converged, the plan's, the robots') at idx[j], QP rows at j
 hipError_t launch_srbd_linesearch(const srbd_model_params& p, const srbd_linesearch_params& ls,
                                   int batch, int N, double* xs, double* us, const double* dx,
                                   const double* du, double* alpha, double* merit, int* converged,
                                   hipStream_t stream, const int* done = nullptr,
                                   const srbd_plan_f64* plan = nullptr,
-                                  const srbd_robots_f64* robots = nullptr);
-hipError_t launch_nmpc_prep(int batch, int N, int it, const double* xs, const double* x0,
+                                  const srbd_robots_f64* robots = nullptr, const int* idx = nullptr);
+// init: every robot's done / sqp_iter / converged start at 0 (not read with idx)
+hipError_t launch_nmpc_prep(int batch, int N, bool init, const double* xs, const double* x0,
                             double* dx0, int* done, int* sqp_iter, int* converged,
-                            hipStream_t stream);
+                            hipStream_t stream, const int* idx = nullptr);
 hipError_t launch_nmpc_after(int batch, int it, const int* conv, int* done, int* sqp_iter,
                              int* converged, int* active, hipStream_t stream);
+// the robots an active set steps (mask, fallen: either may be NULL), listed ascending in idx, *count
+// of them; done = not stepped, sqp_iter = converged = 0 for every robot
+hipError_t launch_nmpc_select_first(int batch, const int* mask, const int* fallen, int* done, int* sqp_iter,
+                                    int* converged, int* idx, int* count, hipStream_t stream);
+// launch_nmpc_after over the n robots of cur[], and those that still iterate listed in next[]
+hipError_t launch_nmpc_select_next(int n, int it, const int* cur, const int* conv, int* done, int* sqp_iter,
+                                   int* converged, int* next, int* count, hipStream_t stream);
 hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, int mode,
                                  const double* xs, const double* us,
                                  const srbd_qp_data_f64& out, hipStream_t stream,
                                  const srbd_plan_f64* plan = nullptr,
-                                 const srbd_robots_f64* robots = nullptr);
+                                 const srbd_robots_f64* robots = nullptr, const int* idx = nullptr);
 
 // srbd_rollout.hip: one tick's plant step and shift of the guess (srbd_qp_srbd_advance_f64).
 // The per-robot outputs carry a stride (doubles / ints per robot), so that the rollout writes

@@ -14,46 +14,20 @@
 // srbd_qp_settings.f32_iters (fp64 solves): the fp64 data narrowed once to fp32 for
 // the first IPM iterations, the fp32 iterate widened back for the fp64 ones.
 #include "kernels.h"
+#include "select.h"
 
 #include <hip/hip_runtime.h>
 
 namespace srbd {
 namespace {
 
-constexpr int kSelThreads = 1024;
-
-// One workgroup walks the batch in 1024-QP tiles: per wave a ballot of the
-// unsolved flags and its prefix popcount, per tile a 16-entry prefix over the
-// waves, so idx[] lists the unsolved QPs in ascending order (deterministic).
+// One workgroup walks the batch in 1024-QP tiles (select.h), so idx[] lists the unsolved QPs
+// in ascending order (deterministic).
 __global__ __launch_bounds__(kSelThreads) void select_unsolved_kernel(const int* __restrict__ status,
                                                                       int batch, int min_status,
                                                                       int* __restrict__ idx,
                                                                       int* __restrict__ count) {
-  __shared__ int wave_tot[kSelThreads / 64];
-  __shared__ int wave_off[kSelThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base_out = 0;
-  for (int base = 0; base < batch; base += kSelThreads) {
-    const int i = base + (int)threadIdx.x;
-    const bool flag = i < batch && status[i] >= min_status;
-    const unsigned long long m = __ballot(flag);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int run = 0;
-      for (int w = 0; w < kSelThreads / 64; ++w) {
-        wave_off[w] = run;
-        run += wave_tot[w];
-      }
-      wave_tot[0] = run;  // tile total (wave_tot is re-written next tile after the barrier)
-    }
-    __syncthreads();
-    if (flag) idx[base_out + wave_off[wave] + before] = i;
-    base_out += wave_tot[0];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = base_out;
+  select_in_order(batch, idx, count, [&](int i, int&) { return status[i] >= min_status; });
 }
 
 __global__ void gather_widen_kernel(const float* __restrict__ src, double* __restrict__ dst,

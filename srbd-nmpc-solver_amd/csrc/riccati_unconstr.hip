@@ -49,12 +49,12 @@ hipError_t prepare_riccati_device() {
 }
 
 template <>
-hipError_t launch_riccati_unconstr<double>(const ProblemArgsT<double>& a, hipStream_t stream) {
-  return ric_f64::launch(a, stream);
+hipError_t launch_riccati_unconstr<double>(const ProblemArgsT<double>& a, hipStream_t stream, bool streaming) {
+  return ric_f64::launch(a, stream, streaming);
 }
 template <>
-hipError_t launch_riccati_unconstr<float>(const ProblemArgsT<float>& a, hipStream_t stream) {
-  return ric_f32::launch(a, stream);
+hipError_t launch_riccati_unconstr<float>(const ProblemArgsT<float>& a, hipStream_t stream, bool streaming) {
+  return ric_f32::launch(a, stream, streaming);
 }
 template <>
 hipError_t launch_unconstr_residuals<double>(const ProblemArgsT<double>& a, hipStream_t stream) {
@@ -81,6 +81,7 @@ bool unconstr_reads_once<float>(const ProblemArgsT<float>& a) {
   return ric_f32::reads_once(a);
 }
 bool latency_server_ok(const ProblemArgsT<double>& a) { return ric_f64::server_ok(a); }
+int riccati_single_qp_batch_max() { return ric_f64::single_qp_batch_max(); }
 hipError_t launch_latency_server(const ProblemArgsT<double>& a, LatMailbox* mb, int epoch, int last_done,
                                  long long idle_ticks, long long life_ticks, hipStream_t stream) {
   return ric_f64::launch_server(a, mb, epoch, last_done, idle_ticks, life_ticks, stream);

@@ -944,7 +944,18 @@ bool reads_once(const ProblemArgsT<real>& a) {
 }
 
 template <bool SQRT>
-static hipError_t launch_alg(const ProblemArgsT<real>& a, hipStream_t stream) {
+static hipError_t launch_streaming(const ProblemArgsT<real>& a, hipStream_t stream) {
+  const int threads = 256;
+  const long long lanes = (long long)a.batch * kGroup;
+  const int blocks = (int)((lanes + threads - 1) / threads);
+  hipLaunchKernelGGL(riccati_unconstr_kernel<SQRT>, dim3(blocks), dim3(threads), 0, stream, a);
+  return hipGetLastError();
+}
+
+// streaming: the streaming kernel whatever the batch size (launch() below)
+template <bool SQRT>
+static hipError_t launch_alg(const ProblemArgsT<real>& a, hipStream_t stream, bool streaming) {
+  if (streaming) return launch_streaming<SQRT>(a, stream);
 #if SRBD_WITH_LATENCY
   if (!SQRT && lat_eligible(a)) {
     if (fused_residuals(a)) {
@@ -970,11 +981,7 @@ static hipError_t launch_alg(const ProblemArgsT<real>& a, hipStream_t stream) {
                        stream, a);
     return hipGetLastError();
   }
-  const int threads = 256;
-  const long long lanes = (long long)a.batch * kGroup;
-  const int blocks = (int)((lanes + threads - 1) / threads);
-  hipLaunchKernelGGL(riccati_unconstr_kernel<SQRT>, dim3(blocks), dim3(threads), 0, stream, a);
-  return hipGetLastError();
+  return launch_streaming<SQRT>(a, stream);
 }
 
 #if SRBD_WITH_LATENCY
@@ -1029,12 +1036,17 @@ hipError_t prepare_device() {
   return e;
 }
 
-hipError_t launch(const ProblemArgsT<real>& a, hipStream_t stream) {
+// streaming: not the single-QP kernels of small batches -- a sub-batch of a large batch is then
+// solved by the kernel the large batch takes, with its bits (the NMPC step's compaction); the
+// residuals are then never fused
+hipError_t launch(const ProblemArgsT<real>& a, hipStream_t stream, bool streaming) {
   if (a.batch <= 0) return hipSuccess;
   // 12 x 12 stages only: smaller problems arrive embedded by pad.hip
   if (a.nx != 12 || a.nu != 12) return hipErrorInvalidValue;
-  return a.ric_alg ? launch_alg<true>(a, stream) : launch_alg<false>(a, stream);
+  return a.ric_alg ? launch_alg<true>(a, stream, streaming) : launch_alg<false>(a, stream, streaming);
 }
+// the largest batch the single-QP kernels take
+constexpr int single_qp_batch_max() { return kLdsBatchMax; }
 
 }  // namespace SRBD_NS
 }  // namespace srbd

@@ -15,6 +15,7 @@
 // srbd-nmpc-solver_amd/srbd_model.py.
 #include "../../include/srbd_qp.h"
 #include "kernels.h"
+#include "select.h"
 namespace {
 // The QP blocks (8 GB at 65536 x 20) are read back by the solve from HBM whatever the
 // write policy, so they are streamed past the caches (linearise 2.19 -> 2.14 ms, A/B).
@@ -36,9 +37,27 @@ struct LinArgs {
   srbd_qp_data_f64 out;  // device pointers to fill (const dropped below)
   double qf_scale;
 };
-// with a plan, its four pointers follow the block; with robots, their six
-template <bool PLAN, bool ROBOT>
-struct LinArgsT : LinArgs, PlanArgs<PLAN>, RobotArgs<ROBOT> {};
+// A subset (the NMPC step's compaction): QP j of the launch belongs to robot
+// idx[j].  Kernels that read or write per-robot rows take a `bool SUBSET` beside PLAN and ROBOT:
+// false is the code without (QP j is robot j, no index is loaded), true reads and writes the
+// robot's rows (xs, us, x0, alpha, converged, the plan's and the robots' rows) at idx[j] and the
+// QP's rows (the QP data, dx0, the solution) at j.
+struct NoSubset {};
+struct SubsetIdx {
+  const int* idx;
+};
+template <bool SUBSET>
+using SubsetArgs = std::conditional_t<SUBSET, SubsetIdx, NoSubset>;
+template <bool SUBSET>
+__device__ __forceinline__ int robot_of(const SubsetArgs<SUBSET>& s, int qp) {
+  if constexpr (SUBSET)
+    return s.idx[qp];
+  else
+    return qp;
+}
+// with a plan, its four pointers follow the block; with robots, their six; with a subset, idx
+template <bool PLAN, bool ROBOT, bool SUBSET>
+struct LinArgsT : LinArgs, PlanArgs<PLAN>, RobotArgs<ROBOT>, SubsetArgs<SUBSET> {};
 
 // Per-stage descriptor of the matrices a (QP, stage) thread hands to its wave: the
 // nonzero 3x3 Jacobian blocks and the friction-barrier R (diagonal + 4 off-diagonal pairs
@@ -119,8 +138,10 @@ __device__ __forceinline__ double r_at(const double* d, int i, int j) {
 // threads, adjacent memory.
 // With robots, the thread loads its robot's scalars at qp: a wave holds stages of several
 // robots, so they are per-lane values; the N threads of one robot read the same addresses.
-template <bool PLAN, bool ROBOT>
-__global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, LinArgsT<PLAN, ROBOT> a) {
+// With a subset, the thread reads its robot's x, u, plan and robot rows at idx[qp]; everything
+// it and the wave write is QP data, at t.
+template <bool PLAN, bool ROBOT, bool SUBSET>
+__global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, LinArgsT<PLAN, ROBOT, SUBSET> a) {
   constexpr int kD = ROBOT ? kDescRobot : kDesc;
   __shared__ double desc[kLinThreads * kD];
   const int N = a.N;
@@ -132,11 +153,14 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
   if (t < nst_all) {
     const int qp = (int)(t / N), k = (int)(t % N);
     double* dsc = desc + threadIdx.x * kD;
-    const double* x = a.xs + ((size_t)qp * (N + 1) + k) * 12;
-    const double* u = a.us + (size_t)t * 12;
+    const int rq = robot_of<SUBSET>(a, qp);
+    size_t rt = (size_t)t;  // the robot's stage row
+    if constexpr (SUBSET) rt = (size_t)rq * N + k;
+    const double* x = a.xs + ((size_t)rq * (N + 1) + k) * 12;
+    const double* u = a.us + rt * 12;
     const double* xn = x + 12;
-    const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)t);
-    const RobotVals<ROBOT> rb = load_robot<ROBOT>(p, a, (size_t)qp);
+    const StageVals<PLAN> sv = load_stage<PLAN>(p, a, rt);
+    const RobotVals<ROBOT> rb = load_robot<ROBOT>(p, a, (size_t)rq);
     // ---- shooting dynamics (GetShootingDynamic, SRBD_model.cpp:178-235): b = RK4(x, u) - x_next ----
     {
       double k1[12], k2[12], k3[12], k4[12], xt[12];
@@ -291,15 +315,21 @@ __global__ void __launch_bounds__(kLinThreads) srbd_lin_stage_kernel(Model m, Li
 // N; prepareQpStructures, NMPC_solver.cpp:286-313), element-wise and coalesced; with the
 // cone, the terminal stage's rows are absent (masked).
 // With a plan, x_ref is read at the same element index e as xs.
-// With robots, the weight is element i of row blk / (N + 1) of Q or Qf.
-__device__ __forceinline__ double cost_w(const srbd_model_params& p, const srbd_robots_f64& rb, long long blk,
-                                         int N, int k, int i) {
+// With robots, the weight is element i of the robot's row (blk / (N + 1)) of Q or Qf.
+// With a subset, that row, xs and x_ref are the robot's, idx[blk / (N + 1)]; Q and q are written at the QP's.
+template <bool SUBSET>
+__device__ __forceinline__ double cost_w(const srbd_model_params& p, const srbd_robots_f64& rb,
+                                         const SubsetArgs<SUBSET>& sub, long long blk, int N, int k, int i) {
   const double* wr = k < N ? rb.Q : rb.Qf;
-  if (wr) return wr[(size_t)(blk / (N + 1)) * 12 + i];
+  if constexpr (SUBSET) {
+    if (wr) return wr[(size_t)sub.idx[blk / (N + 1)] * 12 + i];
+  } else {
+    if (wr) return wr[(size_t)(blk / (N + 1)) * 12 + i];
+  }
   return k < N ? p.Q[i] : p.Qf[i];
 }
-template <bool PLAN, bool ROBOT>
-__global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PLAN, ROBOT> a) {
+template <bool PLAN, bool ROBOT, bool SUBSET>
+__global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PLAN, ROBOT, SUBSET> a) {
   const srbd_model_params& p = m.p;
   const int N = a.N;
   const long long nq2 = (long long)a.batch * (N + 1) * 72;  // double2 of Q
@@ -313,7 +343,7 @@ __global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PL
     if constexpr (ROBOT) {
       // every lane loads both weights and selects: loading only in the 12 of a block's 72 pairs
       // that hold a diagonal element was slower (0.47 against 0.44 ms at 65536 x 20)
-      const double w0 = cost_w(p, a, blk, N, k, i), w1 = cost_w(p, a, blk, N, k, i + 1);
+      const double w0 = cost_w<SUBSET>(p, a, a, blk, N, k, i), w1 = cost_w<SUBSET>(p, a, a, blk, N, k, i + 1);
       st_nt(&reinterpret_cast<double2*>(const_cast<double*>(a.out.Q))[g], i == j ? sc * w0 : 0.0,
             i + 1 == j ? sc * w1 : 0.0);
     } else {
@@ -326,14 +356,16 @@ __global__ void __launch_bounds__(256) srbd_lin_cost_kernel(Model m, LinArgsT<PL
     const long long blk = e / 12;
     const int i = (int)(e - blk * 12), k = (int)(blk % (N + 1));
     const double sc = k < N ? 1.0 : a.qf_scale;
+    size_t er = (size_t)e;  // the element of the robot's xs and x_ref
+    if constexpr (SUBSET) er = ((size_t)a.idx[blk / (N + 1)] * (N + 1) + k) * 12 + i;
     double wi;
     if constexpr (ROBOT) {
-      wi = cost_w(p, a, blk, N, k, i);
+      wi = cost_w<SUBSET>(p, a, a, blk, N, k, i);
     } else {
       const double* w = k < N ? p.Q : p.Qf;
       wi = w[i];
     }
-    const_cast<double*>(a.out.q)[e] = sc * wi * (a.xs[e] - x_ref_at<PLAN>(p, a, (size_t)e, i));
+    const_cast<double*>(a.out.q)[e] = sc * wi * (a.xs[er] - x_ref_at<PLAN>(p, a, er, i));
   } else if (a.mode == 2 && g < nq2 + nq + (long long)a.batch * 24) {
     const long long e = g - nq2 - nq;
     const long long qp = e / 24;
@@ -369,8 +401,8 @@ struct LsArgs {
   double qf_scale;
   const int* done;  // optional: robots whose SQP loop has stopped are left untouched
 };
-template <bool PLAN, bool ROBOT>
-struct LsArgsT : LsArgs, PlanArgs<PLAN>, RobotArgs<ROBOT> {};
+template <bool PLAN, bool ROBOT, bool SUBSET>
+struct LsArgsT : LsArgs, PlanArgs<PLAN>, RobotArgs<ROBOT>, SubsetArgs<SUBSET> {};
 
 // the 24 friction-cone / torque-limit rows f(u) of GetConstrain (SRBD_model.cpp:237-260,
 // R_f = I), two nonzeros each: the explicit form of bc(c) + sum_j ac(c, j) u_j
@@ -420,12 +452,14 @@ __device__ __forceinline__ void cone_grad(const srbd_model_params& p, double mu,
 // With a plan the stage's rows are loaded here, once for the four slopes.
 // With robots, rb holds the lane's mass, L^-1, mu and R across the trial loop; the weights are
 // read here from the robot's row of Q or Qf.
-template <bool PLAN, bool ROBOT>
-__device__ void stage_merit(const Model& m, const LsArgsT<PLAN, ROBOT>& a, const RobotVals<ROBOT>& rb, int qp,
-                            int k, double al, bool grad, double& phi, double& theta, double& dphi) {
+// With a subset, x, u and the plan's rows are the robot's (idx[qp]); dx, du are the QP's.
+template <bool PLAN, bool ROBOT, bool SUBSET>
+__device__ void stage_merit(const Model& m, const LsArgsT<PLAN, ROBOT, SUBSET>& a, const RobotVals<ROBOT>& rb,
+                            int qp, int k, double al, bool grad, double& phi, double& theta, double& dphi) {
   const srbd_model_params& p = m.p;
   const int N = a.N;
-  const double* x = a.xs + ((size_t)qp * (N + 1) + k) * 12;
+  const int rq = robot_of<SUBSET>(a, qp);
+  const double* x = a.xs + ((size_t)rq * (N + 1) + k) * 12;
   const double* dx = a.dx + ((size_t)qp * (N + 1) + k) * 12;
   double xa[12];
   #pragma unroll
@@ -434,7 +468,7 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN, ROBOT>& a, const
   const double sc = k < N ? 1.0 : a.qf_scale;
   #pragma unroll
   for (int i = 0; i < 12; ++i) {
-    const double e = xa[i] - x_ref_at<PLAN>(p, a, ((size_t)qp * (N + 1) + k) * 12 + i, i);
+    const double e = xa[i] - x_ref_at<PLAN>(p, a, ((size_t)rq * (N + 1) + k) * 12 + i, i);
     double wi;
     if constexpr (ROBOT)
       wi = rb.w(p, k == N, i);
@@ -444,11 +478,11 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN, ROBOT>& a, const
     if (grad) dphi += dx[i] * sc * wi * e;
   }
   if (k == N) return;
-  const double* u = a.us + ((size_t)qp * N + k) * 12;
+  const double* u = a.us + ((size_t)rq * N + k) * 12;
   const double* du = a.du + ((size_t)qp * N + k) * 12;
-  const double* xn = a.xs + ((size_t)qp * (N + 1) + k + 1) * 12;
+  const double* xn = a.xs + ((size_t)rq * (N + 1) + k + 1) * 12;
   const double* dxn = a.dx + ((size_t)qp * (N + 1) + k + 1) * 12;
-  const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)qp * N + k);
+  const StageVals<PLAN> sv = load_stage<PLAN>(p, a, (size_t)rq * N + k);
   double ua[12];
   #pragma unroll
   for (int i = 0; i < 12; ++i) ua[i] = u[i] + al * du[i];
@@ -507,28 +541,33 @@ __device__ void stage_merit(const Model& m, const LsArgsT<PLAN, ROBOT>& a, const
 
 // With a plan, lane l reads the plan rows of its own stages l, l + 32, ...
 // With robots, every lane of the group loads its robot's scalars once, before the loops.
-template <bool PLAN, bool ROBOT>
-__global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PLAN, ROBOT> a) {
+// With a subset, the group of QP qp works on robot idx[qp]: its xs, us, alpha, merit and
+// converged rows (a listed robot is never done: `done` is not read).
+template <bool PLAN, bool ROBOT, bool SUBSET>
+__global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PLAN, ROBOT, SUBSET> a) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int qp = gid / kLsGroup, lane = gid % kLsGroup;
   if (qp >= a.batch) return;
-  if (a.done && a.done[qp]) return;  // group-uniform
+  if constexpr (!SUBSET) {
+    if (a.done && a.done[qp]) return;  // group-uniform
+  }
+  const int rq = robot_of<SUBSET>(a, qp);
   const int N = a.N;
   const srbd_linesearch_params& ls = a.ls;
-  const RobotVals<ROBOT> rb = load_robot<ROBOT>(m.p, a, (size_t)qp);
+  const RobotVals<ROBOT> rb = load_robot<ROBOT>(m.p, a, (size_t)rq);
   // merit at the current iterate
   double phi = 0.0, theta = 0.0, dphi = 0.0;
   for (int k = lane; k <= N; k += kLsGroup)
-    stage_merit<PLAN, ROBOT>(m, a, rb, qp, k, 0.0, true, phi, theta, dphi);
+    stage_merit<PLAN, ROBOT, SUBSET>(m, a, rb, qp, k, 0.0, true, phi, theta, dphi);
   phi = gsum32(phi);
   theta = gsum32(theta);
   dphi = gsum32(dphi);
-  double alpha = a.alpha[qp];
+  double alpha = a.alpha[rq];
   double accepted = -1.0;  // accepted step length, -1: none
   while (alpha > ls.alpha_min) {
     double pa = 0.0, ta = 0.0, unused = 0.0;
     for (int k = lane; k <= N; k += kLsGroup)
-      stage_merit<PLAN, ROBOT>(m, a, rb, qp, k, alpha, false, pa, ta, unused);
+      stage_merit<PLAN, ROBOT, SUBSET>(m, a, rb, qp, k, alpha, false, pa, ta, unused);
     pa = gsum32(pa);
     ta = gsum32(ta);
     bool ok;
@@ -547,24 +586,24 @@ __global__ void __launch_bounds__(64) srbd_linesearch_kernel(Model m, LsArgsT<PL
   }
   if (accepted > 0.0) {
     for (int k = lane; k <= N; k += kLsGroup) {
-      double* x = a.xs + ((size_t)qp * (N + 1) + k) * 12;
+      double* x = a.xs + ((size_t)rq * (N + 1) + k) * 12;
       const double* dx = a.dx + ((size_t)qp * (N + 1) + k) * 12;
       for (int i = 0; i < 12; ++i) x[i] += accepted * dx[i];
       if (k < N) {
-        double* u = a.us + ((size_t)qp * N + k) * 12;
+        double* u = a.us + ((size_t)rq * N + k) * 12;
         const double* du = a.du + ((size_t)qp * N + k) * 12;
         for (int i = 0; i < 12; ++i) u[i] += accepted * du[i];
       }
     }
   }
   if (lane == 0) {
-    a.alpha[qp] = alpha;
+    a.alpha[rq] = alpha;
     if (a.merit) {
-      a.merit[(size_t)qp * 3 + 0] = phi;
-      a.merit[(size_t)qp * 3 + 1] = theta;
-      a.merit[(size_t)qp * 3 + 2] = dphi;
+      a.merit[(size_t)rq * 3 + 0] = phi;
+      a.merit[(size_t)rq * 3 + 1] = theta;
+      a.merit[(size_t)rq * 3 + 2] = dphi;
     }
-    if (a.converged) a.converged[qp] = (dphi > -1e-3 && theta < 1e-6) ? 1 : 0;
+    if (a.converged) a.converged[rq] = (dphi > -1e-3 && theta < 1e-6) ? 1 : 0;
   }
 }
 
@@ -576,22 +615,28 @@ bool plan_given(const srbd_plan_f64* plan) {
 bool robots_given(const srbd_robots_f64* rb) {
   return rb && (rb->mass || rb->Lbody || rb->mu || rb->Q || rb->Qf || rb->R);
 }
-// Fill the kernel's argument block from its three parts and launch the (PLAN, ROBOT) instantiation.
-template <bool PLAN, bool ROBOT, class Base, class Launch>
-void with_args(const Base& a, const srbd_plan_f64* plan, const srbd_robots_f64* robots, Launch&& launch) {
-  std::conditional_t<std::is_same_v<Base, LinArgs>, LinArgsT<PLAN, ROBOT>, LsArgsT<PLAN, ROBOT>> full;
+// Fill the kernel's argument block from its four parts and launch the (PLAN, ROBOT, SUBSET) instantiation.
+template <bool PLAN, bool ROBOT, bool SUBSET, class Base, class Launch>
+void with_args(const Base& a, const srbd_plan_f64* plan, const srbd_robots_f64* robots, const int* idx,
+               Launch&& launch) {
+  std::conditional_t<std::is_same_v<Base, LinArgs>, LinArgsT<PLAN, ROBOT, SUBSET>, LsArgsT<PLAN, ROBOT, SUBSET>> full;
   static_cast<Base&>(full) = a;
   if constexpr (PLAN) static_cast<srbd_plan_f64&>(full) = *plan;
   if constexpr (ROBOT) static_cast<srbd_robots_f64&>(full) = *robots;
+  if constexpr (SUBSET) static_cast<SubsetIdx&>(full).idx = idx;
   launch(full);
 }
-// the four instantiations: fn is called with std::bool_constant<PLAN>, std::bool_constant<ROBOT>
+// the eight instantiations: fn is called with std::bool_constant<PLAN>, <ROBOT>, <SUBSET>
 template <class Fn>
-void dispatch(bool plan, bool robot, Fn&& fn) {
-  if (plan && robot) fn(std::true_type{}, std::true_type{});
-  else if (plan) fn(std::true_type{}, std::false_type{});
-  else if (robot) fn(std::false_type{}, std::true_type{});
-  else fn(std::false_type{}, std::false_type{});
+void dispatch(bool plan, bool robot, bool subset, Fn&& fn) {
+  auto with_subset = [&](auto PL, auto RB) {
+    if (subset) fn(PL, RB, std::true_type{});
+    else fn(PL, RB, std::false_type{});
+  };
+  if (plan && robot) with_subset(std::true_type{}, std::true_type{});
+  else if (plan) with_subset(std::true_type{}, std::false_type{});
+  else if (robot) with_subset(std::false_type{}, std::true_type{});
+  else with_subset(std::false_type{}, std::false_type{});
 }
 
 }  // namespace
@@ -600,36 +645,43 @@ hipError_t launch_srbd_linesearch(const srbd_model_params& p, const srbd_linesea
                                   int batch, int N, double* xs, double* us, const double* dx,
                                   const double* du, double* alpha, double* merit, int* converged,
                                   hipStream_t stream, const int* done, const srbd_plan_f64* plan,
-                                  const srbd_robots_f64* robots) {
+                                  const srbd_robots_f64* robots, const int* idx) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
   const LsArgs a{batch, N, xs, us, dx, du, alpha, merit, converged, ls, p.qf_scale, done};
   const long long n = (long long)batch * kLsGroup;
   const int threads = 64;
   const dim3 grid((unsigned)((n + threads - 1) / threads));
-  dispatch(plan_given(plan), robots_given(robots), [&](auto PL, auto RB) {
-    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value;
-    with_args<kP, kR>(a, plan, robots, [&](const auto& full) {
-      hipLaunchKernelGGL((srbd_linesearch_kernel<kP, kR>), grid, dim3(threads), 0, stream, m, full);
+  dispatch(plan_given(plan), robots_given(robots), idx != nullptr, [&](auto PL, auto RB, auto SB) {
+    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value, kS = decltype(SB)::value;
+    with_args<kP, kR, kS>(a, plan, robots, idx, [&](const auto& full) {
+      hipLaunchKernelGGL((srbd_linesearch_kernel<kP, kR, kS>), grid, dim3(threads), 0, stream, m, full);
     });
   });
   return hipGetLastError();
 }
 
 // ---- the SQP loop of NMPCSolver::controlLoop (NMPC_solver.cpp:362-372) ----
-// Before iteration `it`: the QP's initial state x0 - x_nmpc(:, 0)
-// (NMPC_solver.cpp:320); at it == 0 every robot is active.
-__global__ void __launch_bounds__(256) nmpc_prep_kernel(int batch, int N, int it, const double* xs,
+// Before an iteration: the QP's initial state x0 - x_nmpc(:, 0) (NMPC_solver.cpp:320); with
+// `init` (iteration 0 of a step without an active set) every robot starts iterating.
+// With a subset, QP j's dx0 is robot idx[j]'s, and the loop state is the selection's.
+template <bool SUBSET>
+__global__ void __launch_bounds__(256) nmpc_prep_kernel(int batch, int N, int init, const double* xs,
                                                          const double* x0, double* dx0, int* done,
-                                                         int* sqp_iter, int* converged) {
+                                                         int* sqp_iter, int* converged, const int* idx) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= batch * 12) return;
   const int r = gid / 12, i = gid % 12;
-  dx0[gid] = x0[gid] - xs[(size_t)r * (N + 1) * 12 + i];
-  if (it == 0 && i == 0) {
-    done[r] = 0;
-    sqp_iter[r] = 0;
-    converged[r] = 0;
+  if constexpr (SUBSET) {
+    const size_t rq = (size_t)idx[r];
+    dx0[gid] = x0[rq * 12 + i] - xs[rq * (N + 1) * 12 + i];
+  } else {
+    dx0[gid] = x0[gid] - xs[(size_t)r * (N + 1) * 12 + i];
+    if (init && i == 0) {
+      done[r] = 0;
+      sqp_iter[r] = 0;
+      converged[r] = 0;
+    }
   }
 }
 
@@ -651,13 +703,52 @@ __global__ void __launch_bounds__(256) nmpc_after_kernel(int batch, int it, cons
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(active, (int)__popcll(m));
 }
 
-hipError_t launch_nmpc_prep(int batch, int N, int it, const double* xs, const double* x0,
+// ---- active sets (srbd_qp_srbd_set_active_f64): the lists of the robots that iterate ----
+// Before iteration 0 of a step with an active set: robot r is stepped iff (mask == NULL or
+// mask[r] != 0) and (fallen == NULL or fallen[r] == 0).  Every robot's loop state is written
+// (done = not stepped, sqp_iter = converged = 0); idx lists the stepped robots in ascending
+// order and *count holds how many.  One workgroup (select.h).
+__global__ void __launch_bounds__(kSelThreads) nmpc_select_first_kernel(int batch, const int* mask,
+                                                                         const int* fallen, int* done,
+                                                                         int* sqp_iter, int* converged,
+                                                                         int* idx, int* count) {
+  select_in_order(batch, idx, count, [&](int r, int&) {
+    const bool on = (!mask || mask[r] != 0) && (!fallen || fallen[r] == 0);
+    done[r] = on ? 0 : 1;
+    sqp_iter[r] = 0;
+    converged[r] = 0;
+    return on;
+  });
+}
+// After the line search of iteration `it` over the n listed robots: nmpc_after_kernel's
+// bookkeeping for robot cur[j], and the robots that have not converged listed in next[], in
+// cur's (ascending) order, *count of them.
+__global__ void __launch_bounds__(kSelThreads) nmpc_select_next_kernel(int n, int it, const int* cur,
+                                                                        const int* conv, int* done,
+                                                                        int* sqp_iter, int* converged,
+                                                                        int* next, int* count) {
+  select_in_order(n, next, count, [&](int j, int& r) {
+    r = cur[j];
+    const int c = conv[r];
+    sqp_iter[r] = it + 1;
+    converged[r] = c;
+    done[r] = c;
+    return c == 0;
+  });
+}
+
+hipError_t launch_nmpc_prep(int batch, int N, bool init, const double* xs, const double* x0,
                             double* dx0, int* done, int* sqp_iter, int* converged,
-                            hipStream_t stream) {
+                            hipStream_t stream, const int* idx) {
   if (batch <= 0) return hipSuccess;
   const long long n = (long long)batch * 12;
-  hipLaunchKernelGGL(nmpc_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                     batch, N, it, xs, x0, dx0, done, sqp_iter, converged);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (idx)
+    hipLaunchKernelGGL(nmpc_prep_kernel<true>, grid, dim3(256), 0, stream, batch, N, 0, xs, x0, dx0, done,
+                       sqp_iter, converged, idx);
+  else
+    hipLaunchKernelGGL(nmpc_prep_kernel<false>, grid, dim3(256), 0, stream, batch, N, init ? 1 : 0, xs, x0,
+                       dx0, done, sqp_iter, converged, idx);
   return hipGetLastError();
 }
 
@@ -671,10 +762,26 @@ hipError_t launch_nmpc_after(int batch, int it, const int* conv, int* done, int*
   return hipGetLastError();
 }
 
+hipError_t launch_nmpc_select_first(int batch, const int* mask, const int* fallen, int* done, int* sqp_iter,
+                                    int* converged, int* idx, int* count, hipStream_t stream) {
+  if (batch <= 0) return hipSuccess;
+  hipLaunchKernelGGL(nmpc_select_first_kernel, dim3(1), dim3(kSelThreads), 0, stream, batch, mask, fallen,
+                     done, sqp_iter, converged, idx, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_nmpc_select_next(int n, int it, const int* cur, const int* conv, int* done, int* sqp_iter,
+                                   int* converged, int* next, int* count, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(nmpc_select_next_kernel, dim3(1), dim3(kSelThreads), 0, stream, n, it, cur, conv, done,
+                     sqp_iter, converged, next, count);
+  return hipGetLastError();
+}
+
 hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, int mode,
                                  const double* xs, const double* us,
                                  const srbd_qp_data_f64& out, hipStream_t stream,
-                                 const srbd_plan_f64* plan, const srbd_robots_f64* robots) {
+                                 const srbd_plan_f64* plan, const srbd_robots_f64* robots, const int* idx) {
   if (batch <= 0) return hipSuccess;
   Model m{p};
   const LinArgs a{batch, N, mode, xs, us, out, p.qf_scale};
@@ -686,12 +793,12 @@ hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, i
   const long long nst = (long long)batch * N;
   const long long ncost = (long long)batch * (N + 1) * (72 + 12) + (mode == 2 ? (long long)batch * 24 : 0);
   const dim3 gstage((unsigned)((nst + kLinThreads - 1) / kLinThreads)), gcost((unsigned)((ncost + 255) / 256));
-  dispatch(plan_given(plan), robots_given(robots), [&](auto PL, auto RB) {
-    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value;
-    with_args<kP, kR>(a, plan, robots, [&](const auto& full) {
-      hipLaunchKernelGGL((srbd_lin_stage_kernel<kP, kR>), gstage, dim3(kLinThreads), 0, stream, m,
+  dispatch(plan_given(plan), robots_given(robots), idx != nullptr, [&](auto PL, auto RB, auto SB) {
+    constexpr bool kP = decltype(PL)::value, kR = decltype(RB)::value, kS = decltype(SB)::value;
+    with_args<kP, kR, kS>(a, plan, robots, idx, [&](const auto& full) {
+      hipLaunchKernelGGL((srbd_lin_stage_kernel<kP, kR, kS>), gstage, dim3(kLinThreads), 0, stream, m,
                          full);
-      hipLaunchKernelGGL((srbd_lin_cost_kernel<kP, kR>), gcost, dim3(256), 0, stream, m, full);
+      hipLaunchKernelGGL((srbd_lin_cost_kernel<kP, kR, kS>), gcost, dim3(256), 0, stream, m, full);
     });
   });
   return hipGetLastError();
