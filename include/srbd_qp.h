@@ -19,6 +19,8 @@
  *                        hpipm-cpp shim calls for one QP or a small batch).
  *   srbd_qp_solve_f32 / _host_f32  the fp32 twins (HPIPM's s_ocp_qp_ipm_solve,
  *                        hpipm_s_ocp_qp_ipm.h:238).
+ *   srbd_qp_solve_backward_f64  nothing in the reference: the gradients of the QP data through
+ *                        the solve (one more Riccati solve and outer products).
  *   srbd_qp_destroy      ~OcpQpIpmSolver (d_ocp_qp_*_wrapper frees).
  *   srbd_qp_status_string  hpipm::to_string(HpipmStatus) (:19-33).
  * The steps either side of the solve in the reference's SQP iteration, batched:
@@ -388,6 +390,60 @@ int srbd_qp_solve_soft_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* 
 int srbd_qp_solve_soft_host_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
                                 const srbd_qp_data_f64* data, const srbd_qp_soft_f64* soft,
                                 const srbd_qp_solution_f64* sol, const srbd_qp_slack_f64* slack);
+
+/* ------------------------------------------------------------------------
+ * Backward pass (additive to ABI 12): the gradients of a scalar l of the solution with respect
+ * to the QP data, from the cotangents gx = dl/dx [batch][N+1][nx] and gu = dl/du [batch][N][nu]
+ * (the mpc.pytorch / OptNet pattern: learn cost weights or model matrices through the QP).
+ * pi[k+1] multiplies A x[k] + B u[k] + b[k] - x[k+1] = 0 and pi[0] multiplies x0 - x[0] = 0.
+ * The adjoint QP has the same A, B, Q, S, R with q := gx, r := gu, b := 0, x0 := 0; with its
+ * solution (dx, du, dpi) and the forward solution (x, u, pi), per stage k:
+ *   grad q = dx                  grad r = du           grad b = dpi[k+1]       grad x0 = dpi[0]
+ *   grad Q = 1/2 (dx x' + x dx')   (k = 0..N)          grad R = 1/2 (du u' + u du')
+ *   grad S = du x' + u dx'   (nu x nx)
+ *   grad A = pi[k+1] dx' + dpi[k+1] x'                 grad B = pi[k+1] du' + dpi[k+1] u'
+ * dx[0] = 0, so grad q and grad Q are exactly zero at stage 0.  grad Q and grad R are the
+ * gradients with respect to a symmetric matrix: a caller who moves Q_ij and Q_ji together sees
+ * grad Q_ij + grad Q_ji.
+ * Input boxes (a handle with has_box_u): input (k, i) is active iff its bound is unmasked and
+ * u - lbu < act_tol or ubu - u < act_tol.  The adjoint QP is then solved on a masked copy of the
+ * stages that pins du = 0 there, the way a missing input is padded: column i of B and row i of S
+ * cleared, row and column i of R cleared with 1 on the diagonal, entry i of r cleared.  The
+ * formulas are unchanged.  The result is the gradient of the problem with that active set held
+ * fixed; where a bound is weakly active it is undefined, which is the caller's concern.
+ * The grad arrays are device memory in the layout of the inputs they belong to (column-major
+ * blocks); any may be NULL and is then neither formed nor written.  gx or gu may be NULL (zero),
+ * not both.  data is the forward call's, sol its x, u, pi (read only; the other fields are not
+ * read).  Of the settings only reg_prim and ric_alg are read: the adjoint factorises what the
+ * forward solve factorised.
+ * Asynchronous on `stream` like srbd_qp_solve_f64, whose workspace it uses: it follows the
+ * forward solve on the same stream, one call at a time per handle.  The adjoint solution and
+ * the masked stages live in a buffer the handle allocates on first use (srbd_qp_memory_bytes
+ * counts it): per QP 2 (N+1) nx + N nu doubles and (N+1) max(nx, nu) zeros, and with has_box_u
+ * N (2 nx nu + nu nu + nu) more, 71 KB per QP at N = 20, nx = nu = 12.
+ * Checks: a NULL handle, data, sol, grad or settings, A...x0 or x / u / pi missing, lbu / ubu
+ * missing on a handle with has_box_u, both cotangents NULL, act_tol negative or not finite:
+ * SRBD_QP_EINVAL; a handle with ng > 0, has_box_x or the stage-major layout: SRBD_QP_EDIM; batch
+ * above the capacity: SRBD_QP_ECAPACITY; batch == 0: SRBD_QP_OK.  A failed check launches and
+ * writes nothing.
+ * Out of scope: general rows, state boxes, soft boxes, gradients with respect to the bounds, a
+ * cotangent for pi, P or K, fp32 and the mixed-precision settings, the stage-major layout,
+ * srbd_qp_multi_*, the hpipm-cpp shim, and the NMPC step (its SQP loop and line search).
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_qp_grad_f64 {   /* device, outputs, same layout as the inputs; any may be NULL */
+  double *A, *B, *b, *Q, *S, *R, *q, *r, *x0;
+} srbd_qp_grad_f64;
+
+int srbd_qp_solve_backward_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
+                               const srbd_qp_data_f64* data,        /* the forward call's data            */
+                               const srbd_qp_solution_f64* sol,     /* the forward x, u, pi (read only)   */
+                               const double* gx, const double* gu,  /* cotangents; either may be NULL = 0 */
+                               double act_tol,                      /* >= 0, finite; read with has_box_u  */
+                               const srbd_qp_grad_f64* grad, void* stream);
+/* The number of inputs the last srbd_qp_solve_backward_f64 on this handle pinned, per QP:
+ * count [batch] (device), copied on `stream` behind that call.  SRBD_QP_EINVAL without
+ * has_box_u, or for more QPs than that call had; batch == 0 returns SRBD_QP_OK.               */
+int srbd_qp_backward_pinned_f64(srbd_qp_handle h, int batch, int* count, void* stream);
 
 /* ------------------------------------------------------------------------
  * Device-side SRBD linearisation: the producer of the QP data, i.e.

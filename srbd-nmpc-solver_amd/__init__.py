@@ -10,6 +10,7 @@ Python package is the host-side mirror used by tests and bench.py:
 * :mod:`.capi` -- ctypes binding of libsrbd_qp.so (device pointers from torch).
 * :mod:`.srbd_model` -- seeded SRBD QP generator (the reference's linearisation).
 * :mod:`.dist` -- rank sharding / solution gather of the multi-GPU bench.
+* :mod:`.diff` -- the solve as a torch.autograd.Function (srbd_qp_solve_backward_f64).
 
 The reference's C++ interface (``hpipm::OcpQpIpmSolver`` & co.) is rebuilt in
 ``hpipm-cpp/`` (libhpipm-cpp.so) on top of the same C-ABI.
@@ -24,7 +25,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # lazy: importing the package must work on a CPU-only host (tests, build()).
-    if name in ("capi", "srbd_model", "dist"):
+    if name in ("capi", "srbd_model", "dist", "diff"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -69,6 +69,14 @@ class Slack(C.Structure):
     _fields_ = [(n, _dp) for n in SLACK_FIELDS]
 
 
+# the backward pass's outputs (srbd_qp_grad_f64; the header's field order): NULL = not asked for
+GRAD_FIELDS = ("A", "B", "b", "Q", "S", "R", "q", "r", "x0")
+
+
+class Grad(C.Structure):
+    _fields_ = [(n, _dp) for n in GRAD_FIELDS]
+
+
 # srbd_qp_solve_host_cb_f64's callback: void (*)(void* ctx)
 FACTORS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
@@ -428,6 +436,8 @@ def _prototypes():
         "srbd_qp_solve_host_f32": (i, [h, i, st, d32, s32], always),
         "srbd_qp_solve_soft_f64": (i, [h, i, st, d64, P(Soft), s64, P(Slack), vp], maybe),  # soft boxes
         "srbd_qp_solve_soft_host_f64": (i, [h, i, st, d64, P(Soft), s64, P(Slack)], maybe),
+        "srbd_qp_solve_backward_f64": (i, [h, i, st, d64, s64, vp, vp, C.c_double, P(Grad), vp], maybe),  # backward
+        "srbd_qp_backward_pinned_f64": (i, [h, i, vp, vp], maybe),
         "srbd_qp_solve_host_cb_f64": (i, [h, i, st, d64, s64, FACTORS_CB, vp], maybe),  # ABI 12
         "srbd_qp_host_staging_f64": (i, [h, i, st, d64, s64], maybe),  # ABI 10
         "srbd_qp_multi_create": (i, [P(Dims), i, P(i), i, P(vp)], maybe),  # ABI 10
@@ -572,6 +582,30 @@ class Handle:
                                            C.byref(slack) if slack is not None else None,
                                            C.c_void_p(stream or None)), "srbd_qp_solve_soft_f64")
         _order_after(o)
+
+    def solve_backward_device(self, batch: int, settings: Settings, data: Data, sol: Solution, gx, gu,
+                              grad: Grad, act_tol: float = 0.0, stream: int = 0, order: bool = True) -> None:
+        """srbd_qp_solve_backward_f64: the gradients of the QP data from the cotangents gx = dl/dx,
+        gu = dl/du (torch fp64 device tensors or device addresses; either may be None = zero) at
+        the forward solution in `sol`, into the non-NULL fields of `grad`.  Launched and ordered
+        like solve_device, behind the forward solve on the same stream."""
+        ptr = lambda t: C.c_void_p((t if isinstance(t, int) else _tensor_ptr(t)) or None)
+        o = _order_before(self, stream, order)
+        check(lib().srbd_qp_solve_backward_f64(self._h, int(batch), C.byref(settings), C.byref(data), C.byref(sol),
+                                               ptr(gx), ptr(gu), float(act_tol), C.byref(grad),
+                                               C.c_void_p(stream or None)), "srbd_qp_solve_backward_f64")
+        _order_after(o)
+
+    def backward_pinned(self, batch: int, stream: int = 0, order: bool = True):
+        """srbd_qp_backward_pinned_f64: an int32 device tensor [batch], the inputs the last
+        solve_backward_device on this handle (has_box_u) pinned per QP."""
+        import torch
+        count = torch.empty(int(batch), dtype=torch.int32, device=torch.device("cuda", self.device))
+        o = _order_before(self, stream, order)
+        check(lib().srbd_qp_backward_pinned_f64(self._h, int(batch), C.c_void_p(count.data_ptr()),
+                                                C.c_void_p(stream or None)), "srbd_qp_backward_pinned_f64")
+        _order_after(o)
+        return count
 
     def solve_soft_host(self, batch: int, settings: Settings, data: Data, soft: Soft, sol: Solution,
                         slack: Optional[Slack] = None) -> None:

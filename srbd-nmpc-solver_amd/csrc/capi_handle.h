@@ -1,7 +1,8 @@
 // capi_handle.h -- what the translation units of the C-ABI (include/srbd_qp.h) share: the
 // handle and its buffers, the error helpers, and the few functions that cross between
-// srbd_qp_capi.hip (handle, settings), capi_solve.hip (device-pointer solves), capi_host.hip
-// (host-buffer solves, the resident server) and capi_srbd.hip (the SRBD entry points).
+// srbd_qp_capi.hip (handle, settings), capi_solve.hip (device-pointer solves), capi_backward.hip
+// (their backward pass), capi_host.hip (host-buffer solves, the resident server) and
+// capi_srbd.hip (the SRBD entry points).
 // Private to the library: nothing declared here is exported but srbd::set_error.
 #pragma once
 
@@ -93,10 +94,15 @@ struct srbd_qp_handle_s {
   srbd::Buffer mixed;
   // the latency IPM's lq_fact 1 switch: the compact batch for the batched kernels
   srbd::Buffer lqsw;
+  // srbd_qp_solve_backward_f64: the adjoint solution, its zero b / x0 and, with input boxes, the
+  // masked stages and the pinned counts (capacity QPs); bwd_counted: the QPs whose counts the
+  // last backward pass wrote (srbd_qp_backward_pinned_f64)
+  srbd::Buffer bwd;
+  int bwd_counted = 0;
   template <typename F>
   void each_buffer(F&& f) {
     for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &roll, &roll_plan, &resc, &resc2, &mixed,
-                            &lqsw})
+                            &lqsw, &bwd})
       f(*b);
   }
   int* nmpc_active_host = nullptr;  // pinned
