@@ -426,7 +426,8 @@ int srbd_qp_solve_soft_host_f64(srbd_qp_handle h, int batch, const srbd_qp_setti
  * SRBD_QP_EINVAL; a handle with ng > 0, has_box_x or the stage-major layout: SRBD_QP_EDIM; batch
  * above the capacity: SRBD_QP_ECAPACITY; batch == 0: SRBD_QP_OK.  A failed check launches and
  * writes nothing.
- * Out of scope: general rows, state boxes, soft boxes, gradients with respect to the bounds, a
+ * General rows on the inputs and the gradients of D and the bounds: srbd_qp_solve_backward_rows_f64
+ * below.  Out of scope: rows on the states (C), state boxes, soft boxes, a
  * cotangent for pi, P or K, fp32 and the mixed-precision settings, the stage-major layout,
  * srbd_qp_multi_*, the hpipm-cpp shim, and the NMPC step (its SQP loop and line search).
  * ---------------------------------------------------------------------- */
@@ -444,6 +445,66 @@ int srbd_qp_solve_backward_f64(srbd_qp_handle h, int batch, const srbd_qp_settin
  * count [batch] (device), copied on `stream` behind that call.  SRBD_QP_EINVAL without
  * has_box_u, or for more QPs than that call had; batch == 0 returns SRBD_QP_OK.               */
 int srbd_qp_backward_pinned_f64(srbd_qp_handle h, int batch, int* count, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Backward pass through general rows on the inputs, and the gradients of D and of the bounds
+ * (additive to ABI 12).  srbd_qp_solve_backward_f64 with two more outputs structs and any ng in
+ * 0..64 with C == NULL (rows on u only: the friction cone of SRBD_QP_SRBD_CONE), with or without
+ * has_box_u, in the QP-major layout.
+ * Signs are those above; the Lagrangian gains  + nu_k' (E_k u_k - e_k).  E_k holds the active
+ * rows of stage k = 0..N-1: a unit row for each pinned input (the rule above), then row j of D_k
+ * for each active general row: its bound is unmasked and D_j u - lg_j < act_tol or
+ * ug_j - D_j u < act_tol.  e_k is the bound that is active: the nearer one, the lower on a tie.
+ * lg[N], ug[N] are never active (C == NULL) and get gradient 0.
+ * The adjoint QP is the one above with E_k du_k = 0 added; dnu_k are its multipliers.  The nine
+ * formulas are unchanged (the true A ... R, the forward x, u, pi, the adjoint dx, du, dpi), and
+ *   grad D_j = dnu_j u' + nu_j du'        for an active general row j
+ *   grad lg_j = -dnu_j  if the lower bound is the active one,  grad ug_j = -dnu_j  if the upper
+ *   grad lbu_i, grad ubu_i: the same for a pinned input
+ * and every entry of an inactive row or bound is exactly 0.  Neither multiplier needs the IPM's
+ * lam.  With E_k' = Y T (Y orthonormal, T upper triangular):
+ *   rho  = R u  + S x  + r  + B' pi[k+1]      nu  = -T^-1 Y' rho
+ *   rho~ = R du + S dx + gu + B' dpi[k+1]     dnu = -T^-1 Y' rho~
+ * The constrained adjoint is still one unconstrained Riccati solve, on the stages
+ *   B~ = B P,  S~ = P S,  R~ = P R P + (I - P),  r~ = P gu,   P = I - Y Y'
+ * (the rotated form with Qf = [Z Y], its Y part cleared like a missing input, written in the
+ * caller's coordinates: du = Z w comes out of the solve).  A stage without an accepted general
+ * row is cleared exactly as above, so on a handle with ng == 0, or when no row is active, the
+ * nine gradients are bit for bit those of srbd_qp_solve_backward_f64.
+ * Dependent rows: pins come first, ascending; then the active general rows, ascending, each
+ * restricted to the unpinned coordinates.  A row is accepted iff the norm of its part orthogonal
+ * to the rows already accepted exceeds rank_tol times its own norm and fewer than nu rows are
+ * accepted so far; otherwise it is dropped: nu = dnu = 0 and its gradients are 0.  The gradient
+ * at such a point is not defined (the caller's concern, like a weakly active bound); the result
+ * is finite.
+ * grad and grad_rows: device memory in the layout of the inputs (grad D: [batch][N][ng*nu],
+ * grad lg / ug: [batch][N+1][ng], grad lbu / ubu: [batch][N][nu]); any field may be NULL and
+ * costs nothing then; one that is passed is fully written, zeros included.  Either struct may be
+ * NULL, not both.
+ * Checks, in this order: those of srbd_qp_solve_backward_f64 with the same codes and messages,
+ * except that ng > 0 is accepted; in addition a rank_tol outside [0, 1) or not finite is
+ * SRBD_QP_EINVAL (after act_tol), data->C != NULL on a handle with ng > 0 is SRBD_QP_EDIM (where
+ * ng > 0 was rejected), and D, lg or ug missing with ng > 0 is SRBD_QP_EINVAL (after lbu / ubu).
+ * A failed check launches and writes nothing.
+ * Asynchronous on `stream`, like srbd_qp_solve_backward_f64 and under the same contract.  The
+ * handle's backward buffer holds the projected stages whenever has_box_u or ng > 0, and three
+ * ints per QP; no factor is stored: the kernel that writes grad_rows forms it again from D.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_qp_grad_rows_f64 {   /* device, outputs, layout of the inputs; any may be NULL */
+  double *D, *lg, *ug, *lbu, *ubu;
+} srbd_qp_grad_rows_f64;
+
+int srbd_qp_solve_backward_rows_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
+                                    const srbd_qp_data_f64* data, const srbd_qp_solution_f64* sol,
+                                    const double* gx, const double* gu, double act_tol,
+                                    double rank_tol,                     /* in [0, 1)                   */
+                                    const srbd_qp_grad_f64* grad,        /* the nine; may be NULL       */
+                                    const srbd_qp_grad_rows_f64* grad_rows, /* may be NULL, not both    */
+                                    void* stream);
+/* What the last srbd_qp_solve_backward_rows_f64 on this handle found, per QP: count [batch][3]
+ * (device): inputs pinned, general rows accepted, general rows dropped; copied on `stream` behind
+ * that call.  SRBD_QP_EINVAL for more QPs than that call had; batch == 0 returns SRBD_QP_OK.   */
+int srbd_qp_backward_active_f64(srbd_qp_handle h, int batch, int* count, void* stream);
 
 /* ------------------------------------------------------------------------
  * Device-side SRBD linearisation: the producer of the QP data, i.e.

@@ -77,6 +77,14 @@ class Grad(C.Structure):
     _fields_ = [(n, _dp) for n in GRAD_FIELDS]
 
 
+# the gradients of the rows and bounds (srbd_qp_grad_rows_f64; the header's field order)
+GRAD_ROWS_FIELDS = ("D", "lg", "ug", "lbu", "ubu")
+
+
+class GradRows(C.Structure):
+    _fields_ = [(n, _dp) for n in GRAD_ROWS_FIELDS]
+
+
 # srbd_qp_solve_host_cb_f64's callback: void (*)(void* ctx)
 FACTORS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
@@ -438,6 +446,9 @@ def _prototypes():
         "srbd_qp_solve_soft_host_f64": (i, [h, i, st, d64, P(Soft), s64, P(Slack)], maybe),
         "srbd_qp_solve_backward_f64": (i, [h, i, st, d64, s64, vp, vp, C.c_double, P(Grad), vp], maybe),  # backward
         "srbd_qp_backward_pinned_f64": (i, [h, i, vp, vp], maybe),
+        "srbd_qp_solve_backward_rows_f64": (i, [h, i, st, d64, s64, vp, vp, C.c_double, C.c_double, P(Grad),
+                                                P(GradRows), vp], maybe),  # general rows, bounds
+        "srbd_qp_backward_active_f64": (i, [h, i, vp, vp], maybe),
         "srbd_qp_solve_host_cb_f64": (i, [h, i, st, d64, s64, FACTORS_CB, vp], maybe),  # ABI 12
         "srbd_qp_host_staging_f64": (i, [h, i, st, d64, s64], maybe),  # ABI 10
         "srbd_qp_multi_create": (i, [P(Dims), i, P(i), i, P(vp)], maybe),  # ABI 10
@@ -604,6 +615,34 @@ class Handle:
         o = _order_before(self, stream, order)
         check(lib().srbd_qp_backward_pinned_f64(self._h, int(batch), C.c_void_p(count.data_ptr()),
                                                 C.c_void_p(stream or None)), "srbd_qp_backward_pinned_f64")
+        _order_after(o)
+        return count
+
+    def solve_backward_rows_device(self, batch: int, settings: Settings, data: Data, sol: Solution, gx, gu,
+                                   grad: Optional[Grad] = None, grad_rows: Optional[GradRows] = None,
+                                   act_tol: float = 0.0, rank_tol: float = 1e-8, stream: int = 0,
+                                   order: bool = True) -> None:
+        """srbd_qp_solve_backward_rows_f64: solve_backward_device on a handle that may have general
+        rows on the inputs (ng > 0, C = NULL), with the gradients of D, lg, ug, lbu, ubu into the
+        non-NULL fields of `grad_rows`.  `grad` or `grad_rows` may be None, not both."""
+        ptr = lambda t: C.c_void_p((t if isinstance(t, int) else _tensor_ptr(t)) or None)
+        ref = lambda s: C.byref(s) if s is not None else None
+        o = _order_before(self, stream, order)
+        check(lib().srbd_qp_solve_backward_rows_f64(self._h, int(batch), C.byref(settings), C.byref(data),
+                                                    C.byref(sol), ptr(gx), ptr(gu), float(act_tol), float(rank_tol),
+                                                    ref(grad), ref(grad_rows), C.c_void_p(stream or None)),
+              "srbd_qp_solve_backward_rows_f64")
+        _order_after(o)
+
+    def backward_active(self, batch: int, stream: int = 0, order: bool = True):
+        """srbd_qp_backward_active_f64: an int32 device tensor [batch][3], what the last
+        solve_backward_rows_device on this handle found per QP: inputs pinned, general rows
+        accepted, general rows dropped."""
+        import torch
+        count = torch.empty(int(batch), 3, dtype=torch.int32, device=torch.device("cuda", self.device))
+        o = _order_before(self, stream, order)
+        check(lib().srbd_qp_backward_active_f64(self._h, int(batch), C.c_void_p(count.data_ptr()),
+                                                C.c_void_p(stream or None)), "srbd_qp_backward_active_f64")
         _order_after(o)
         return count
 

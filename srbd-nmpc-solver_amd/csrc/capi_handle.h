@@ -96,9 +96,11 @@ struct srbd_qp_handle_s {
   srbd::Buffer lqsw;
   // srbd_qp_solve_backward_f64: the adjoint solution, its zero b / x0 and, with input boxes, the
   // masked stages and the pinned counts (capacity QPs); bwd_counted: the QPs whose counts the
-  // last backward pass wrote (srbd_qp_backward_pinned_f64)
+  // last backward pass wrote (srbd_qp_backward_pinned_f64); bwd_active: the same for the three
+  // counts of srbd_qp_solve_backward_rows_f64 (srbd_qp_backward_active_f64)
   srbd::Buffer bwd;
   int bwd_counted = 0;
+  int bwd_active = 0;
   template <typename F>
   void each_buffer(F&& f) {
     for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &roll, &roll_plan, &resc, &resc2, &mixed,

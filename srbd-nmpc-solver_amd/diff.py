@@ -1,8 +1,11 @@
 """The batched QP solve as a differentiable torch function (srbd_qp_solve_f64 forward,
-srbd_qp_solve_backward_f64 backward).
+srbd_qp_solve_backward_f64 or srbd_qp_solve_backward_rows_f64 backward).
 
     x, u, pi = solve_qp(handle, A, B, b, Q, S, R, q, r, x0)
     loss(x, u).backward()        # A.grad, ..., x0.grad for the inputs that require grad
+
+With general rows on the inputs (a handle with ng > 0) D, lg, ug are inputs too, and they and
+lbu, ubu receive gradients.
 
 Both passes run the HIP kernels on the handle's device; nothing is computed by torch.
 """
@@ -16,11 +19,16 @@ __all__ = ["solve_qp"]
 
 _INPUTS = capi.GRAD_FIELDS  # A, B, b, Q, S, R, q, r, x0: the differentiable inputs, in this order
 _BOUNDS = ("lbu", "ubu", "lbu_mask", "ubu_mask")
+_ROWS = ("D", "lg", "ug", "lg_mask", "ug_mask")
+_TENSORS = _INPUTS + _BOUNDS + _ROWS
+_ROW_GRADS = capi.GRAD_ROWS_FIELDS  # D, lg, ug, lbu, ubu: differentiable through the rows entry point
+_LEAD = 4  # forward's arguments before the tensors: handle, settings, act_tol, rank_tol
 
 
 def _shapes(dims):
-    N, nx, nu = dims.N, dims.nx, dims.nu
-    return {"A": (N, nx, nx), "B": (N, nu, nx), "b": (N, nx), "Q": (N + 1, nx, nx), "S": (N, nx, nu),
+    N, nx, nu, ng = dims.N, dims.nx, dims.nu, dims.ng
+    rows = {"D": (N, nu, ng), "lg": (N + 1, ng), "ug": (N + 1, ng), "lg_mask": (N + 1, ng), "ug_mask": (N + 1, ng)}
+    return {**rows, "A": (N, nx, nx), "B": (N, nu, nx), "b": (N, nx), "Q": (N + 1, nx, nx), "S": (N, nx, nu),
             "R": (N, nu, nu), "q": (N + 1, nx), "r": (N, nu), "x0": (nx,),
             "lbu": (N, nu), "ubu": (N, nu), "lbu_mask": (N, nu), "ubu_mask": (N, nu)}
 
@@ -30,8 +38,8 @@ def _make_function():
 
     class _SolveQp(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, handle, settings, act_tol, *tensors):
-            named = dict(zip(_INPUTS + _BOUNDS, tensors))
+        def forward(ctx, handle, settings, act_tol, rank_tol, *tensors):
+            named = dict(zip(_TENSORS, tensors))
             A = named["A"]
             batch, dims = A.shape[0], handle.dims
             new = lambda *shape: torch.zeros(batch, *shape, dtype=torch.float64, device=A.device)
@@ -39,7 +47,7 @@ def _make_function():
             data = capi.Data(**{k: capi._tensor_ptr(named.get(k)) or None for k in capi.DATA_FIELDS})
             sol = capi.Solution(x=x.data_ptr(), u=u.data_ptr(), pi=pi.data_ptr())
             handle.solve_device(batch, settings, data, sol)
-            ctx.handle, ctx.settings, ctx.act_tol = handle, settings, act_tol
+            ctx.handle, ctx.settings, ctx.act_tol, ctx.rank_tol = handle, settings, act_tol, rank_tol
             ctx.save_for_backward(*[t for t in tensors if t is not None], x, u, pi)
             ctx.present = [t is not None for t in tensors]
             ctx.mark_non_differentiable(pi)
@@ -50,23 +58,30 @@ def _make_function():
             saved = list(ctx.saved_tensors)
             x, u, pi = saved[-3:]
             it = iter(saved[:-3])
-            named = dict(zip(_INPUTS + _BOUNDS, [next(it) if p else None for p in ctx.present]))
-            none = (None,) * (3 + len(_INPUTS) + len(_BOUNDS))
+            named = dict(zip(_TENSORS, [next(it) if p else None for p in ctx.present]))
+            none = (None,) * (_LEAD + len(_TENSORS))
             if gx is None and gu is None:
                 return none
-            # (handle, settings, act_tol) come first in forward's arguments
-            wanted = [n for n, need in zip(_INPUTS, ctx.needs_input_grad[3:3 + len(_INPUTS)]) if need]
-            if not wanted:
+            needs = dict(zip(_TENSORS, ctx.needs_input_grad[_LEAD:]))
+            wanted = [n for n in _INPUTS if needs[n]]
+            wanted_rows = [n for n in _ROW_GRADS if needs[n]]
+            if not wanted and not wanted_rows:
                 return none
             gx = None if gx is None else gx.contiguous()
             gu = None if gu is None else gu.contiguous()
-            out = {n: torch.empty_like(named[n]) for n in wanted}
+            out = {n: torch.empty_like(named[n]) for n in wanted + wanted_rows}
             batch = x.shape[0]
             data = capi.Data(**{k: capi._tensor_ptr(named.get(k)) or None for k in capi.DATA_FIELDS})
             sol = capi.Solution(x=x.data_ptr(), u=u.data_ptr(), pi=pi.data_ptr())
-            grad = capi.Grad(**{n: t.data_ptr() for n, t in out.items()})
-            ctx.handle.solve_backward_device(batch, ctx.settings, data, sol, gx, gu, grad, act_tol=ctx.act_tol)
-            return (None, None, None) + tuple(out.get(n) for n in _INPUTS) + (None,) * len(_BOUNDS)
+            grad = capi.Grad(**{n: out[n].data_ptr() for n in wanted})
+            if ctx.handle.dims.ng > 0 or wanted_rows:
+                rows = capi.GradRows(**{n: out[n].data_ptr() for n in wanted_rows})
+                ctx.handle.solve_backward_rows_device(batch, ctx.settings, data, sol, gx, gu, grad if wanted else None,
+                                                      rows if wanted_rows else None, act_tol=ctx.act_tol,
+                                                      rank_tol=ctx.rank_tol)
+            else:  # nothing of the rows: the entry point without them
+                ctx.handle.solve_backward_device(batch, ctx.settings, data, sol, gx, gu, grad, act_tol=ctx.act_tol)
+            return (None,) * _LEAD + tuple(out.get(n) for n in _TENSORS)
 
     return _SolveQp
 
@@ -75,9 +90,10 @@ _function = None
 
 
 def solve_qp(handle, A, B, b, Q, S, R, q, r, x0, lbu=None, ubu=None, lbu_mask=None, ubu_mask=None,
-             settings=None, act_tol=None):
-    """Solve a batch of OCP-QPs on `handle` (a capi.Handle without general rows and state boxes)
-    and return (x, u, pi), differentiable with respect to A, B, b, Q, S, R, q, r and x0.
+             settings=None, act_tol=None, D=None, lg=None, ug=None, lg_mask=None, ug_mask=None, rank_tol=1e-8):
+    """Solve a batch of OCP-QPs on `handle` (a capi.Handle without state boxes and without rows
+    on the states) and return (x, u, pi), differentiable with respect to A, B, b, Q, S, R, q, r and
+    x0, and with respect to D, lg, ug, lbu and ubu.
 
     Every input is a contiguous torch.float64 tensor on the handle's device, in the C-ABI layout
     of include/srbd_qp.h, with a leading batch dimension:
@@ -89,9 +105,14 @@ def solve_qp(handle, A, B, b, Q, S, R, q, r, x0, lbu=None, ubu=None, lbu_mask=No
     gradients come back in the same layout.  Q.grad and R.grad are gradients with respect to a
     symmetric matrix: moving Q_ij and Q_ji together changes the loss by Q.grad_ij + Q.grad_ji.
     lbu, ubu (and the optional 0/1 masks) [B][N][nu] are the input box of a handle with
-    has_box_u; they get no gradient.  The backward pass then holds the active set fixed: an input
-    within act_tol of an unmasked bound is pinned (default sqrt(tol_comp), the slack at which a
-    bound's slack and multiplier are equal when the IPM stops).
+    has_box_u.  The backward pass then holds the active set fixed: an input within act_tol of an
+    unmasked bound is pinned (default sqrt(tol_comp), the slack at which a bound's slack and
+    multiplier are equal when the IPM stops).
+    D [B][N][nu][ng] (column-major ng x nu blocks), lg, ug (and the optional 0/1 masks)
+    [B][N+1][ng] are the general rows lg <= D u <= ug of a handle with ng > 0 (C = 0: rows on the
+    inputs only).  A row within act_tol of an unmasked bound is active; active rows that depend on
+    the pins and on the active rows before them (rank_tol) are dropped.  lbu, ubu, D, lg, ug get
+    gradients; an inactive bound's is exactly zero.  The masks get none.
     settings: a dict for capi.settings_struct, a capi.Settings, or None for the defaults.
     x [B][N+1][nx], u [B][N][nu] carry gradients; pi [B][N+1][nx] is not differentiable.
     Tensors are checked here, with ValueError, before the library sees a pointer."""
@@ -102,12 +123,12 @@ def solve_qp(handle, A, B, b, Q, S, R, q, r, x0, lbu=None, ubu=None, lbu_mask=No
     st = settings if isinstance(settings, capi.Settings) else capi.settings_struct(settings)
     device = torch.device("cuda", handle.device)
     given = dict(A=A, B=B, b=b, Q=Q, S=S, R=R, q=q, r=r, x0=x0, lbu=lbu, ubu=ubu, lbu_mask=lbu_mask,
-                 ubu_mask=ubu_mask)
+                 ubu_mask=ubu_mask, D=D, lg=lg, ug=ug, lg_mask=lg_mask, ug_mask=ug_mask)
     shapes = _shapes(handle.dims)
     batch = None
     for name, t in given.items():
         if t is None:
-            if name not in _BOUNDS:
+            if name in _INPUTS:
                 raise ValueError(f"{name} is required")
             continue
         capi._check_tensor(name, t, (torch.float64,), ("B",) + shapes[name], device, "the handle", any_gpu=True)
@@ -118,6 +139,13 @@ def solve_qp(handle, A, B, b, Q, S, R, q, r, x0, lbu=None, ubu=None, lbu_mask=No
         raise ValueError("lbu and ubu go with a handle created with has_box_u, and only with one")
     if lbu is None and (lbu_mask is not None or ubu_mask is not None):
         raise ValueError("lbu_mask / ubu_mask need lbu and ubu")
+    rows = [n for n in ("D", "lg", "ug") if given[n] is not None]
+    if len(rows) not in (0, 3) or bool(rows) != (handle.dims.ng > 0):
+        raise ValueError("D, lg and ug go with a handle created with ng > 0, and only with one")
+    if not rows and (lg_mask is not None or ug_mask is not None):
+        raise ValueError("lg_mask / ug_mask need D, lg and ug")
+    if not (0.0 <= float(rank_tol) < 1.0):
+        raise ValueError("rank_tol must be in [0, 1)")
     if act_tol is None:
         act_tol = math.sqrt(st.tol_comp)
-    return _function.apply(handle, st, float(act_tol), *[given[n] for n in _INPUTS + _BOUNDS])
+    return _function.apply(handle, st, float(act_tol), float(rank_tol), *[given[n] for n in _TENSORS])
