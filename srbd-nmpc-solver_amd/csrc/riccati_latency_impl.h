@@ -240,6 +240,21 @@ __device__ __forceinline__ void lat_solve(const ProblemArgsT<double>& a, unsigne
         const double yA = cv ? -yv : 0.0;  // -(Y')[c][m]
         Pn = lat_mfma(yA, yB, Pn);
       });
+      // exactly symmetric from its lower triangle, as the batched kernels (solve_qp) and for
+      // their reason: the antisymmetric rounding of A'(P A) would grow by rho(A)^2 per stage.
+      // Through the G / H tile, which is free here; the vector column stays as it is.
+      lds_wave_fence();
+      sfor<0, 3>([&](auto rr) {
+        constexpr int R = decltype(rr)::value;
+        if (cv && g + 4 * R >= c) gh[c * 12 + g + 4 * R] = Pn[R];
+      });
+      lds_wave_fence();
+      sfor<0, 3>([&](auto rr) {
+        constexpr int R = decltype(rr)::value;
+        const double v = gh[(g + 4 * R) * 12 + cc];  // P[c][g + 4 R], of the lower triangle where row < c
+        if (cv && g + 4 * R < c) Pn[R] = v;
+      });
+      lds_wave_fence();
       Pt = Pn;
       tstamp(9);
       // record: P packed, p (the batched kernel's layout)
