@@ -36,6 +36,8 @@
  *   srbd_qp_srbd_rollout_f64     T ticks of the closed receding-horizon loop around the step.
  *   srbd_qp_srbd_set_robots_f64  per-robot mass, inertia, friction and weights for all of the
  *                                above: what the controller believes, and the true robot.
+ *   srbd_qp_srbd_linearize_backward_f64  nothing in the reference: the gradients of the robots'
+ *                                and the plan's values from the cotangents of the QP arrays.
  *   srbd_qp_srbd_gait_plan_f64   the producer of a tick's plan: a velocity command, a gait and
  *                                the measured state in, the window out (Raibert footholds).
  *   srbd_qp_srbd_rollout_gait_f64  the rollout that replans every tick.
@@ -742,6 +744,73 @@ typedef struct srbd_robots_f64 { /* device memory, fp64, dense; NULL field = the
 } srbd_robots_f64;
 enum { SRBD_QP_ROBOTS_MODEL = 0, SRBD_QP_ROBOTS_PLANT = 1 };
 int srbd_qp_srbd_set_robots_f64(srbd_qp_handle h, int role, const srbd_robots_f64* robots);
+
+/* ------------------------------------------------------------------------
+ * Backward pass of the linearisation (additive to ABI 12): the gradients of a scalar l with
+ * respect to what a caller sets per robot (srbd_robots_f64: mass, Lbody, mu, Q, Qf, R) and per
+ * robot and stage (srbd_plan_f64: x_ref, foot_r, foot_l, fz_max), from the cotangents of the QP
+ * arrays srbd_qp_srbd_linearize_plan_f64 writes -- what srbd_qp_solve_backward_f64 /
+ * srbd_qp_solve_backward_rows_f64 return.  With them the chain robots / plan -> linearise ->
+ * solve -> loss is differentiable end to end, one call per link.  The linearisation point xs, us
+ * is held fixed.
+ * For every array X the linearisation writes, cot->X is dl/dX in X's own layout (column-major
+ * blocks).  The result for a parameter theta of robot i is the element-wise inner product
+ * sum_X <cot->X, dX/dtheta> over that robot's blocks as the linearisation writes them: both
+ * (i, j) and (j, i) of a symmetric block count, the convention of grad Q / grad R above.
+ * The gradient is per robot (plan quantities: per robot and stage) whether the forward value came
+ * from the robots / the plan or from srbd_model_params; a caller with one shared value sums over
+ * the batch.  With s = qf_scale (N when <= 0), w_k = Q (k < N) or s Qf (k = N), e = xs - x_ref:
+ *   grad Q_j  = sum_{k<N} (cot Q[k][j][j] + cot q[k][j] e_kj)
+ *   grad Qf_j = s (cot Q[N][j][j] + cot q[N][j] e_Nj)         grad x_ref[k][j] = -w_kj cot q[k][j]
+ * Input cost and friction barrier (stage k < N): v_c (c = 0..23) are the cone rows f(u), a_c row c
+ * of Ac, b', b'' the relaxed barrier's derivatives and b''' = -2 mu_b / v^3 (v > theta_b; else
+ * 0).  The linearisation writes r = R u + sum_c b'_c a_c and R = R I + sum_c b''_c a_c a_c'.  With
+ * s1_c = a_c' cot r, s2_c = a_c' (cot R) a_c and vbar_c = b''_c s1_c + b'''_c s2_c (CONE:
+ * - cot lg[k][c]):
+ *   grad R       = sum_k (tr cot R + cot r . u)
+ *   grad fz_max[k][leg] = vbar_{12 leg + 4}; BOX_U with a plan: + cot ubu[k][6 leg + 2] where
+ *                  fz_max < u_hi[fz] strictly (a tie belongs to u_hi); cot lbu reaches nothing
+ *   grad mu      = sum_k sum_{c % 12 < 4} (vbar_c fz_leg + b'_c cot r[fz_leg]
+ *                  + b''_c e_fz' (cot R + cot R') a_c); CONE: + cot D where D holds mu
+ * Dynamics: A = I + dt J_x is linear in 1 / Lbody (blocks J00, J01), B = dt J_u in the feet
+ * ([p]x blocks) and in 1 / mass; b (the RK4 defect) depends on 1 / Lbody, 1 / mass and the feet
+ * through all four slopes, differentiated in reverse.  grad Lbody_j = -grad (1 / Lbody_j) /
+ * Lbody_j^2 and grad mass = -grad (1 / mass) / mass^2.
+ * Forward values are read exactly as srbd_qp_srbd_linearize_plan_f64 reads them: the handle's
+ * MODEL role, the plan, then params.  Of cot, A, B, b, Q, R, q, r are read, ubu with BOX_U, D and
+ * lg with CONE; any may be NULL (zero); the other fields (S, C, ug, the masks, ...) are ignored.
+ * cot's A, B, R and D are read 16 bytes at a time and must be 16-byte aligned.
+ * An output of grad that is passed is fully written, zeros included; a NULL one costs nothing.
+ * The sums over a robot's stages are formed in a fixed order: the same inputs give the same
+ * bits.  Per-stage partial sums (6 doubles per stage) live in a buffer the handle allocates on
+ * first use, capacity-sized (srbd_qp_memory_bytes counts it).
+ * Asynchronous on the handle's stream or `stream`, like the forward call.  An active set on the
+ * handle is not consulted: the call covers QPs 0..batch-1 of a dense batch.
+ * Checks, before any device work, in the forward call's order and with its codes: NULL h,
+ * params, xs, us, cot or grad: SRBD_QP_EINVAL; a handle without nx = nu = 12: SRBD_QP_EDIM; batch
+ * above the capacity: SRBD_QP_ECAPACITY; unknown constraints, or CONE on a handle without ng = 24:
+ * SRBD_QP_EINVAL.  Then a grad whose fields are all NULL: SRBD_QP_EINVAL; batch == 0: SRBD_QP_OK.
+ * A failed check launches and writes nothing.
+ * Out of scope: gradients with respect to xs, us and x0; the constants that are not per robot
+ * (dt, mu_b, theta_b, Lfx, Lfz, fmin, u_lo, u_hi, qf_scale); the PLANT role, the plant step and
+ * the rollouts; subsets / active sets; fp32; srbd_qp_multi_* and the hpipm-cpp shim.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_lin_grad_f64 {   /* device, outputs; any may be NULL and then costs nothing */
+  double *mass;            /* [batch]        */
+  double *Lbody;           /* [batch][3]     */
+  double *mu;              /* [batch]        */
+  double *Q, *Qf;          /* [batch][12]    */
+  double *R;               /* [batch]        */
+  double *x_ref;           /* [batch][N+1][12] */
+  double *foot_r, *foot_l; /* [batch][N][3]  */
+  double *fz_max;          /* [batch][N][2]  */
+} srbd_lin_grad_f64;
+
+int srbd_qp_srbd_linearize_backward_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                        const srbd_plan_f64* plan /* may be NULL */, int constraints,
+                                        const double* xs, const double* us,
+                                        const srbd_qp_data_f64* cot /* cotangents, fields as in `out` */,
+                                        const srbd_lin_grad_f64* grad, void* stream);
 
 /* ------------------------------------------------------------------------
  * Gait planner (additive to ABI 12): the producer of a tick's plan window.  From a per-robot

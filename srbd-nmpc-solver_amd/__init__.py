@@ -10,7 +10,8 @@ Python package is the host-side mirror used by tests and bench.py:
 * :mod:`.capi` -- ctypes binding of libsrbd_qp.so (device pointers from torch).
 * :mod:`.srbd_model` -- seeded SRBD QP generator (the reference's linearisation).
 * :mod:`.dist` -- rank sharding / solution gather of the multi-GPU bench.
-* :mod:`.diff` -- the solve as a torch.autograd.Function (srbd_qp_solve_backward_f64).
+* :mod:`.diff` -- the solve and the SRBD linearisation as torch.autograd.Functions (srbd_qp_solve_backward_f64,
+  srbd_qp_srbd_linearize_backward_f64).
 
 The reference's C++ interface (``hpipm::OcpQpIpmSolver`` & co.) is rebuilt in
 ``hpipm-cpp/`` (libhpipm-cpp.so) on top of the same C-ABI.

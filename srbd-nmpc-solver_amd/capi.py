@@ -85,6 +85,20 @@ class GradRows(C.Structure):
     _fields_ = [(n, _dp) for n in GRAD_ROWS_FIELDS]
 
 
+# the linearisation's backward outputs (srbd_lin_grad_f64; the header's field order): per field the
+# shape behind the batch dimension, with the horizon N
+LIN_GRAD_FIELDS = ("mass", "Lbody", "mu", "Q", "Qf", "R", "x_ref", "foot_r", "foot_l", "fz_max")
+
+
+class LinGrad(C.Structure):
+    _fields_ = [(n, _dp) for n in LIN_GRAD_FIELDS]
+
+
+def _lin_grad_shape(name, N):
+    return {"mass": (), "Lbody": (3,), "mu": (), "Q": (12,), "Qf": (12,), "R": (), "x_ref": (N + 1, 12),
+            "foot_r": (N, 3), "foot_l": (N, 3), "fz_max": (N, 2)}[name]
+
+
 # srbd_qp_solve_host_cb_f64's callback: void (*)(void* ctx)
 FACTORS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
@@ -467,6 +481,7 @@ def _prototypes():
         "srbd_qp_srbd_advance_f64": (i, [h, i, mp, plan, P(AdvanceStruct)] + [vp] * 5, maybe),  # the closed loop
         "srbd_qp_srbd_rollout_f64": (i, [h, i, mp, plan, ls, st, i, i, P(RolloutStruct)] + [vp] * 4, maybe),
         "srbd_qp_srbd_set_robots_f64": (i, [h, i, P(RobotsStruct)], maybe),
+        "srbd_qp_srbd_linearize_backward_f64": (i, [h, i, mp, plan, i, vp, vp, d64, P(LinGrad), vp], maybe),
         "srbd_qp_srbd_set_terrain_f64": (i, [h, P(TerrainStruct)], maybe),
         "srbd_qp_srbd_terrain_height_f64": (i, [h, i] + [vp] * 4, maybe),
         "srbd_qp_srbd_set_contact_f64": (i, [h, P(ContactStruct)], maybe),
@@ -967,6 +982,78 @@ def srbd_linearize(handle: Handle, xs, us, constraints: str = "none",
                     C.c_void_p(us.data_ptr()), C.byref(data), C.c_void_p(stream or None))
     _order_after(o)
     return t, data
+
+
+# the cotangents srbd_linearize_backward reads, with the shape behind the batch dimension
+def _lin_cot_shapes(N, constraints):
+    shapes = {"A": (N, 144), "B": (N, 144), "b": (N, 12), "Q": (N + 1, 144), "R": (N, 144), "q": (N + 1, 12),
+              "r": (N, 12)}
+    if constraints == "box_u":
+        shapes["ubu"] = (N, 12)
+    elif constraints == "cone":
+        shapes.update(D=(N, 288), lg=(N + 1, 24))
+    return shapes
+
+
+def srbd_linearize_backward(handle: Handle, xs, us, cot: Dict, constraints: str = "none",
+                            params: Optional[ModelParams] = None, plan: Optional[Plan] = None,
+                            want=LIN_GRAD_FIELDS, stream: int = 0, out=None):
+    """srbd_qp_srbd_linearize_backward_f64: the gradients of the handle's MODEL robots' values (mass,
+    Lbody, mu, Q, Qf, R: per robot) and of the plan's (x_ref, foot_r, foot_l, fz_max: per robot and
+    stage) from the cotangents `cot` of the arrays srbd_linearize writes at the same xs, us,
+    constraints, params and plan -- what diff.solve_qp's backward pass returns.
+    cot: {name: tensor} for any of A, B, b, Q, R, q, r (box_u: ubu; cone: D, lg), torch fp64 device
+    tensors with the element counts of srbd_linearize's outputs (a matrix block may be flat or
+    [..][12][12]); a missing or None entry is zero, other names are ignored.
+    want: the outputs to form (LIN_GRAD_FIELDS); `out`: {name: tensor} to write into instead of
+    allocating.  A gradient is per robot whether or not the handle has robots / the call a plan.
+    Asynchronous on the handle's stream: keep the tensors alive like srbd_linearize's.
+    Returns {name: tensor}: mass, mu, R [B], Lbody [B][3], Q, Qf [B][12], x_ref [B][N+1][12],
+    foot_r, foot_l [B][N][3], fz_max [B][N][2]."""
+    import torch
+    if constraints not in SRBD_CONSTRAINTS:
+        raise ValueError(f"unknown constraints {constraints!r}")
+    _check_tensor("xs", xs, (torch.float64,), ("B", None, 12), None, any_gpu=True)
+    B, N = xs.shape[0], xs.shape[1] - 1
+    _check_tensor("us", us, (torch.float64,), (B, N, 12), xs.device)
+    want = tuple(want)
+    unknown = [n for n in want if n not in LIN_GRAD_FIELDS]
+    if unknown or not want:
+        raise ValueError(f"want must name outputs among {LIN_GRAD_FIELDS}, got {want}")
+    plan_ref = _plan_ref(plan, B, N, xs.device)
+    _check_rows(handle, B, "robots")
+    ptrs = {}
+    for name, shape in _lin_cot_shapes(N, constraints).items():
+        t = cot.get(name)
+        if t is None:
+            continue
+        # dtype, contiguity and device by the usual check; a matrix block may be flat or [12][rows]
+        dims = t.dim() if isinstance(t, torch.Tensor) else 0
+        _check_tensor(f"cot[{name!r}]", t, (torch.float64,), (B, shape[0]) + (None,) * max(dims - 2, 0), xs.device,
+                      expected=(B,) + shape)
+        if t.numel() != B * shape[0] * shape[1]:
+            raise ValueError(f"cot[{name!r}] has shape {tuple(t.shape)}, expected {(B,) + shape}")
+        ptrs[name] = t.data_ptr()
+    res = {}
+    for name in want:
+        shape = (B,) + _lin_grad_shape(name, N)
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float64, device=xs.device)
+        else:
+            _check_tensor(f"out[{name!r}]", t, (torch.float64,), shape, xs.device)
+        res[name] = t
+    data = Data(**{k: ptrs.get(k) or None for k in DATA_FIELDS})
+    grad = LinGrad(**{n: t.data_ptr() for n, t in res.items()})
+    p = params or default_model_params()
+    o = _order_before(handle, stream, True)
+    check(lib().srbd_qp_srbd_linearize_backward_f64(handle.ptr, int(B), C.byref(p), plan_ref,
+                                                    SRBD_CONSTRAINTS[constraints], C.c_void_p(xs.data_ptr()),
+                                                    C.c_void_p(us.data_ptr()), C.byref(data), C.byref(grad),
+                                                    C.c_void_p(stream or None)),
+          "srbd_qp_srbd_linearize_backward_f64")
+    _order_after(o)
+    return res
 
 
 def default_linesearch() -> LsParams:

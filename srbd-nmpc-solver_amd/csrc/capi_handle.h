@@ -101,10 +101,12 @@ struct srbd_qp_handle_s {
   srbd::Buffer bwd;
   int bwd_counted = 0;
   int bwd_active = 0;
+  // srbd_qp_srbd_linearize_backward_f64: the per-stage parts of the robots' sums (capacity QPs)
+  srbd::Buffer lin_bwd;
   template <typename F>
   void each_buffer(F&& f) {
     for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &roll, &roll_plan, &resc, &resc2, &mixed,
-                            &lqsw, &bwd})
+                            &lqsw, &bwd, &lin_bwd})
       f(*b);
   }
   int* nmpc_active_host = nullptr;  // pinned

@@ -195,6 +195,36 @@ int srbd_qp_srbd_linearize_f64(srbd_qp_handle h, int batch, const srbd_model_par
   return srbd_qp_srbd_linearize_plan_f64(h, batch, params, nullptr, constraints, xs, us, out, stream);
 }
 
+// The backward pass of the linearisation: the forward call's checks in its order, then the
+// outputs; the robots' sums go through a scratch row per stage.
+int srbd_qp_srbd_linearize_backward_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                        const srbd_plan_f64* plan, int constraints, const double* xs,
+                                        const double* us, const srbd_qp_data_f64* cot,
+                                        const srbd_lin_grad_f64* grad, void* stream) {
+  if (!h || !params || !xs || !us || !cot || !grad) return fail(SRBD_QP_EINVAL, "NULL argument");
+  const srbd_qp_dims& d = h->dims;
+  if (const int rc = check_srbd_call(h, batch, "SRBD linearisation needs nx = nu = 12")) return rc;
+  if (constraints < SRBD_QP_SRBD_NONE || constraints > SRBD_QP_SRBD_CONE)
+    return fail(SRBD_QP_EINVAL, "unknown constraints mode");
+  if (constraints == SRBD_QP_SRBD_CONE && d.ng != 24) return fail(SRBD_QP_EINVAL, "CONE needs ng = 24");
+  const srbd_lin_grad_f64& g = *grad;
+  const bool sums = g.mass || g.Lbody || g.mu || g.R;
+  if (!sums && !g.Q && !g.Qf && !g.x_ref && !g.foot_r && !g.foot_l && !g.fz_max)
+    return fail(SRBD_QP_EINVAL, "linearize_backward: every output of grad is NULL");
+  if (batch == 0) return SRBD_QP_OK;
+  const srbd_model_params p = with_qf_scale(params, d.N);
+  hipStream_t strm = stream_of(h, stream);
+  srbd::DeviceGuard guard(h->device);
+  if (sums) {
+    const hipError_t e = h->lin_bwd.reserve(srbd::lin_backward_part_elems(h->capacity, d.N) * sizeof(double));
+    if (e != hipSuccess) return hip_fail(alloc_code(e), "linearize_backward scratch allocation failed: ", e);
+  }
+  const hipError_t e = srbd::launch_srbd_linearize_backward(p, batch, d.N, constraints, xs, us, *cot, g,
+                                                            h->lin_bwd.as<double>(), strm, plan, &h->robots_model);
+  if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
+  return SRBD_QP_OK;
+}
+
 void srbd_qp_srbd_default_linesearch(srbd_linesearch_params* p) {
   if (!p) return;
   p->theta_max = 1e-6;

@@ -262,6 +262,15 @@ hipError_t launch_srbd_linearize(const srbd_model_params& p, int batch, int N, i
                                  const srbd_qp_data_f64& out, hipStream_t stream,
                                  const srbd_plan_f64* plan = nullptr,
                                  const srbd_robots_f64* robots = nullptr, const int* idx = nullptr);
+// srbd_linearize_backward.hip (srbd_qp_srbd_linearize_backward_f64): the gradients of the robots'
+// and the plan's values from the cotangents `cot` of the arrays launch_srbd_linearize writes.
+// part: lin_backward_part_elems(batch, N) doubles of scratch, read and written only when one of
+// grad's mass, Lbody, mu, R is asked for.
+size_t lin_backward_part_elems(int batch, int N);
+hipError_t launch_srbd_linearize_backward(const srbd_model_params& p, int batch, int N, int mode,
+                                          const double* xs, const double* us, const srbd_qp_data_f64& cot,
+                                          const srbd_lin_grad_f64& grad, double* part, hipStream_t stream,
+                                          const srbd_plan_f64* plan, const srbd_robots_f64* robots);
 
 // srbd_rollout.hip: one tick's plant step and shift of the guess (srbd_qp_srbd_advance_f64).
 // The per-robot outputs carry a stride (doubles / ints per robot), so that the rollout writes

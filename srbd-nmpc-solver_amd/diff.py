@@ -7,6 +7,14 @@ srbd_qp_solve_backward_f64 or srbd_qp_solve_backward_rows_f64 backward; DESIGN.m
 With general rows on the inputs (a handle with ng > 0) D, lg, ug are inputs too, and they and
 lbu, ubu receive gradients.
 
+srbd_linearize is the link before it: the SRBD linearisation as a differentiable function of the
+handle's robots and of the plan (srbd_qp_srbd_linearize_plan_f64 forward,
+srbd_qp_srbd_linearize_backward_f64 backward), so that
+
+    qp = srbd_linearize(handle, xs, us, plan=plan)
+    x, u, pi = solve_qp(handle, x0=x0, **{k: qp[k] for k in ("A", "B", "b", "Q", "S", "R", "q", "r")})
+    loss(x, u).backward()        # robots.mass.grad, robots.Q.grad, plan.fz_max.grad, ...
+
 Both passes run the HIP kernels on the handle's device; nothing is computed by torch.
 """
 from __future__ import annotations
@@ -15,7 +23,7 @@ import math
 
 from . import capi
 
-__all__ = ["solve_qp"]
+__all__ = ["solve_qp", "srbd_linearize"]
 
 _INPUTS = capi.GRAD_FIELDS  # A, B, b, Q, S, R, q, r, x0: the differentiable inputs, in this order
 _BOUNDS = ("lbu", "ubu", "lbu_mask", "ubu_mask")
@@ -149,3 +157,75 @@ def solve_qp(handle, A, B, b, Q, S, R, q, r, x0, lbu=None, ubu=None, lbu_mask=No
     if act_tol is None:
         act_tol = math.sqrt(st.tol_comp)
     return _function.apply(handle, st, float(act_tol), float(rank_tol), *[given[n] for n in _TENSORS])
+
+
+# ---- the linearisation ----
+_LIN_SHAPES = {"A": (12, 12), "B": (12, 12), "b": (12,), "Q": (12, 12), "S": (12, 12), "R": (12, 12), "q": (12,),
+               "r": (12,), "lbu": (12,), "ubu": (12,), "D": (12, 24), "lg": (24,), "ug": (24,), "lg_mask": (24,),
+               "ug_mask": (24,)}
+_LIN_OUT = {"none": ("A", "B", "b", "Q", "S", "R", "q", "r"),
+            "box_u": ("A", "B", "b", "Q", "S", "R", "q", "r", "lbu", "ubu"),
+            "cone": ("A", "B", "b", "Q", "S", "R", "q", "r", "D", "lg", "ug", "lg_mask", "ug_mask")}
+_LIN_CONSTANT = ("S", "lbu", "ug", "lg_mask", "ug_mask")  # no parameter reaches them
+_ROBOT_FIELDS = tuple(capi.Robots.FIELDS)  # mass, Lbody, mu, Q, Qf, R
+_PLAN_FIELDS = tuple(capi.Plan.FIELDS)  # x_ref, foot_r, foot_l, fz_max
+_LIN_LEAD = 7  # forward's arguments before the parameters: handle, constraints, params, plan, robots, xs, us
+
+
+def _make_linearize():
+    import torch
+
+    class _SrbdLinearize(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, handle, constraints, params, plan, robots, xs, us, *leaves):
+            t, _ = capi.srbd_linearize(handle, xs, us, constraints, params=params, plan=plan)
+            ctx.handle, ctx.constraints, ctx.params, ctx.plan, ctx.robots = handle, constraints, params, plan, robots
+            ctx.save_for_backward(xs, us)
+            names = _LIN_OUT[constraints]
+            outs = tuple(t[n].view(*t[n].shape[:2], *_LIN_SHAPES[n]) for n in names)
+            ctx.mark_non_differentiable(*[o for n, o in zip(names, outs) if n in _LIN_CONSTANT])
+            return outs
+
+        @staticmethod
+        def backward(ctx, *grads):
+            none = (None,) * (_LIN_LEAD + len(_ROBOT_FIELDS) + len(_PLAN_FIELDS))
+            names = _ROBOT_FIELDS + _PLAN_FIELDS
+            want = [n for n, need in zip(names, ctx.needs_input_grad[_LIN_LEAD:]) if need]
+            cot = {n: g.contiguous() for n, g in zip(_LIN_OUT[ctx.constraints], grads)
+                   if g is not None and n not in _LIN_CONSTANT}
+            if not want or not cot:
+                return none
+            if getattr(ctx.handle, "_robots", (None, None))[0] is not ctx.robots:
+                raise RuntimeError("srbd_linearize: the handle's model robots were replaced (Handle.set_robots) "
+                                   "between the forward and the backward pass")
+            xs, us = ctx.saved_tensors
+            out = capi.srbd_linearize_backward(ctx.handle, xs, us, cot, ctx.constraints, params=ctx.params,
+                                               plan=ctx.plan, want=want)
+            return none[:_LIN_LEAD] + tuple(out.get(n) for n in names)
+
+    return _SrbdLinearize
+
+
+_linearize = None
+
+
+def srbd_linearize(handle, xs, us, constraints="none", params=None, plan=None):
+    """capi.srbd_linearize as a differentiable function: the QP arrays of the SRBD linearisation at
+    xs [B][N+1][12], us [B][N][12], as a dict of tensors in solve_qp's shapes (A, B, Q, S, R
+    [B][N or N+1][12][12], b, q, r [..][12]; box_u: lbu, ubu [B][N][12]; cone: D [B][N][12][24], lg, ug
+    and the masks [B][N+1][24]; column-major blocks, the C-ABI layout).
+    Gradients go to those tensors of the handle's model robots (Handle.set_robots: mass, Lbody, mu,
+    Q, Qf, R) and of `plan` (x_ref, foot_r, foot_l, fz_max) that require grad; xs and us get none
+    (the linearisation point is held fixed), and S, lbu, ug and the masks are constants.  The
+    backward pass raises RuntimeError if the handle's model robots are no longer the Robots object
+    the forward call saw."""
+    global _linearize
+    if _linearize is None:
+        _linearize = _make_linearize()
+    if constraints not in _LIN_OUT:
+        raise ValueError(f"unknown constraints {constraints!r}")
+    robots = getattr(handle, "_robots", (None, None))[0]
+    leaves = [None if robots is None else getattr(robots, n) for n in _ROBOT_FIELDS]
+    leaves += [None if plan is None else getattr(plan, n) for n in _PLAN_FIELDS]
+    outs = _linearize.apply(handle, constraints, params, plan, robots, xs, us, *leaves)
+    return dict(zip(_LIN_OUT[constraints], outs))
