@@ -13,6 +13,7 @@ theta; it takes the same decisions whenever that margin is far above those bits.
 from __future__ import annotations
 
 import sys
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -70,8 +71,17 @@ class _Margin:
         return a < b
 
 
-def line_search(srbd_model, p, plan, xs, us, dx, du, alpha, ls=None):
-    """One robot.  Returns (xs_new, us_new, alpha_new, phi, theta, dphi, converged, margin)."""
+Trial = namedtuple("Trial", "alpha branch accepted phi_a theta_a phi_clause theta_clause")
+Trial.__doc__ = """One trial step of line_search's trace: its step length, the filter branch it took
+("theta": theta_a > theta_max; "armijo"; "mixed": the rest), whether it was accepted, the merit at
+the trial point, and for the mixed branch each accept clause on its own (phi_a < phi - beta_phi
+theta; theta_a < (1 - beta_theta) theta), else None."""
+
+
+def line_search(srbd_model, p, plan, xs, us, dx, du, alpha, ls=None, trace=None):
+    """One robot.  Returns (xs_new, us_new, alpha_new, phi, theta, dphi, converged, margin).
+    trace: a list that receives one Trial per trial step (none when alpha <= alpha_min on
+    entry); it changes neither the operations nor the margin."""
     ls = dict(LS_DEFAULTS, **(ls or {}))
     N = us.shape[0]
     Ac, bc = srbd_model.friction_cone(p)
@@ -83,18 +93,23 @@ def line_search(srbd_model, p, plan, xs, us, dx, du, alpha, ls=None):
         xa = xs + alpha * dx
         ua = us + alpha * du
         phi_a, theta_a, _, _ = merit(srbd_model, p, plan, xa, ua, N, Ac, bc)
+        clauses = (None, None)
         if m.lt(ls["theta_max"], theta_a):
-            if m.lt(theta_a, (1.0 - ls["beta_theta"]) * theta):
-                xs_new, us_new = xa, ua
-                break
+            branch = "theta"
+            ok = m.lt(theta_a, (1.0 - ls["beta_theta"]) * theta)
         elif m.lt(max(theta_a, theta), ls["theta_min"]) and m.lt(dphi, 0.0):
-            if m.lt(phi_a, phi + ls["eta"] * alpha * dphi):
-                xs_new, us_new = xa, ua
-                break
+            branch = "armijo"
+            ok = m.lt(phi_a, phi + ls["eta"] * alpha * dphi)
         else:
-            if m.lt(phi_a, phi - ls["beta_phi"] * theta) or m.lt(theta_a, (1.0 - ls["beta_theta"]) * theta):
-                xs_new, us_new = xa, ua
-                break
+            branch = "mixed"
+            ok = m.lt(phi_a, phi - ls["beta_phi"] * theta) or m.lt(theta_a, (1.0 - ls["beta_theta"]) * theta)
+            if trace is not None:  # plain comparisons: the second one is not part of the decision above
+                clauses = (phi_a < phi - ls["beta_phi"] * theta, theta_a < (1.0 - ls["beta_theta"]) * theta)
+        if trace is not None:
+            trace.append(Trial(alpha, branch, ok, phi_a, theta_a, *clauses))
+        if ok:
+            xs_new, us_new = xa, ua
+            break
         alpha = ls["beta_alpha"] * alpha
     converged = m.lt(-1e-3, dphi) and m.lt(theta, 1e-6)
     return xs_new, us_new, alpha, phi, theta, dphi, converged, m.smallest

@@ -57,6 +57,29 @@ def host_nmpc(sm, oracle, p, batch, constraints):
                         SQP_MAX_LOOP, constraints) for i in range(xs.shape[0])]
 
 
+def linesearch_matches_host(xs, us, xs_t, us_t, al_t, merit, conv, host):
+    """What srbd_linesearch left on the device against the host restatement, robot by robot.
+    xs, us: the inputs (numpy); xs_t, us_t, al_t: the device tensors after the call, merit and
+    conv its results; host: per robot nmpc_plan_host.line_search's tuple.  Merit rtol 1e-9,
+    alpha and converged exact, an accepted point to 1e-13; a robot without an accepted step
+    (exhausted, or no trial at all) keeps its xs, us bit for bit."""
+    import torch
+    xs_in, us_in = _dev(xs), _dev(us)
+    got_m, got_a, got_c = merit.cpu().numpy(), al_t.cpu().numpy(), conv.cpu().numpy()
+    got_x, got_u = xs_t.cpu().numpy(), us_t.cpu().numpy()
+    assert len(host) == xs.shape[0]
+    for i, (xn, un, an, phi, theta, dphi, cv, margin) in enumerate(host):
+        assert margin > 1e-8, (i, margin)  # the inputs are off every decision boundary
+        np.testing.assert_allclose(got_m[i], [phi, theta, dphi], rtol=1e-9, atol=1e-12, err_msg=str(i))
+        assert got_a[i] == an, (i, got_a[i], an)
+        assert bool(got_c[i]) == cv, i
+        if np.array_equal(xn, xs[i]) and np.array_equal(un, us[i]):  # no step was accepted
+            assert torch.equal(xs_t[i], xs_in[i]) and torch.equal(us_t[i], us_in[i]), i
+        else:
+            np.testing.assert_allclose(got_x[i], xn, rtol=1e-13, atol=1e-13, err_msg=str(i))
+            np.testing.assert_allclose(got_u[i], un, rtol=1e-13, atol=1e-13, err_msg=str(i))
+
+
 # ---- host values as the binding's objects ----
 def device_plan(capi, plan):
     return capi.Plan(**{k: (None if getattr(plan, k) is None else _dev(getattr(plan, k))) for k in FIELDS})

@@ -9,7 +9,7 @@ import pytest
 
 import nmpc_plan_host as PH
 from nmpc_plan_host import NMPC_SEED, constant_plan, random_plan, walking_batch
-from srbd_device import NMPC, SQP_MAX_LOOP, _dev, device_plan, handle, host_nmpc
+from srbd_device import NMPC, SQP_MAX_LOOP, _dev, device_plan, handle, host_nmpc, linesearch_matches_host
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +33,8 @@ def check_linearize(pkg, B, N, seed, constraints, plan):
 
 def check_linesearch(pkg, B, N, seed, plan):
     """srbd_linesearch(plan) against the host restatement, at the tolerances of
-    test_gpu_linesearch.py: merit rtol 1e-9, accepted point 1e-13, alpha exact."""
+    test_gpu_linesearch.py: merit rtol 1e-9, accepted point 1e-13, alpha exact
+    (srbd_device.linesearch_matches_host)."""
     sm = pkg.srbd_model
     p = sm.SrbdParams()
     xs, us, _ = sm.sample_trajectories(B, N, seed, p)
@@ -46,16 +47,8 @@ def check_linesearch(pkg, B, N, seed, plan):
     plan_t = device_plan(pkg.capi, plan)
     merit, conv = pkg.capi.srbd_linesearch(h, xs_t, us_t, dx_t, du_t, al_t, plan=plan_t)
     h.synchronize()
-    for i in range(B):
-        xn, un, an, phi, theta, dphi, cv, margin = PH.line_search(sm, p, plan.robot(i), xs[i], us[i],
-                                                                  dx[i], du[i], float(alpha0[i]))
-        assert margin > 1e-8, (i, margin)  # the inputs are off every decision boundary
-        np.testing.assert_allclose(merit[i].cpu().numpy(), [phi, theta, dphi], rtol=1e-9, atol=1e-12,
-                                   err_msg=str(i))
-        assert al_t[i].item() == an, (i, al_t[i].item(), an)
-        assert bool(conv[i].item()) == cv
-        np.testing.assert_allclose(xs_t[i].cpu().numpy(), xn, rtol=1e-13, atol=1e-13)
-        np.testing.assert_allclose(us_t[i].cpu().numpy(), un, rtol=1e-13, atol=1e-13)
+    host = [PH.line_search(sm, p, plan.robot(i), xs[i], us[i], dx[i], du[i], float(alpha0[i])) for i in range(B)]
+    linesearch_matches_host(xs, us, xs_t, us_t, al_t, merit, conv, host)
 
 
 # ---- 1. linearisation parity: 140 stage threads, three 64-thread blocks, the last partial ----

@@ -11,7 +11,7 @@ import rollout_host as RH
 from nmpc_plan_host import NMPC_SEED, random_plan, walking_batch
 from rollout_host import feet_plan, start
 from srbd_device import (NMPC, SQP_MAX_LOOP, STEP_ATOL_U, STEP_ATOL_X, _dev, caller_loop, close, device_plan,
-                         device_robots, handle, host_nmpc)
+                         device_robots, handle, host_nmpc, linesearch_matches_host)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,14 +51,7 @@ def check_linesearch(pkg, B, N, seed, params, robots_t, plan=None):
     merit, conv = pkg.capi.srbd_linesearch(h, xs_t, us_t, _dev(dx), _dev(du), al_t, plan=plan_t)
     h.synchronize()
     host = BH.line_search(sm, params, plan, xs, us, dx, du, alpha0)
-    for i, (xn, un, an, phi, theta, dphi, cv, margin) in enumerate(host):
-        assert margin > 1e-8, (i, margin)  # the inputs are off every decision boundary
-        np.testing.assert_allclose(merit[i].cpu().numpy(), [phi, theta, dphi], rtol=1e-9, atol=1e-12,
-                                   err_msg=str(i))
-        assert al_t[i].item() == an, (i, al_t[i].item(), an)
-        assert bool(conv[i].item()) == cv
-        np.testing.assert_allclose(xs_t[i].cpu().numpy(), xn, rtol=1e-13, atol=1e-13)
-        np.testing.assert_allclose(us_t[i].cpu().numpy(), un, rtol=1e-13, atol=1e-13)
+    linesearch_matches_host(xs, us, xs_t, us_t, al_t, merit, conv, host)
 
 
 # ---- 1. linearisation: 140 stage threads in three 64-thread blocks, the last partial; robots
