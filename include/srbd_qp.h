@@ -38,6 +38,8 @@
  *                                above: what the controller believes, and the true robot.
  *   srbd_qp_srbd_linearize_backward_f64  nothing in the reference: the gradients of the robots'
  *                                and the plan's values from the cotangents of the QP arrays.
+ *   srbd_qp_srbd_solve_backward_f64  the same gradients straight from the solve and its adjoint:
+ *                                the two backward passes in one, no QP gradient in between.
  *   srbd_qp_srbd_gait_plan_f64   the producer of a tick's plan: a velocity command, a gait and
  *                                the measured state in, the window out (Raibert footholds).
  *   srbd_qp_srbd_rollout_gait_f64  the rollout that replans every tick.
@@ -811,6 +813,62 @@ int srbd_qp_srbd_linearize_backward_f64(srbd_qp_handle h, int batch, const srbd_
                                         const double* xs, const double* us,
                                         const srbd_qp_data_f64* cot /* cotangents, fields as in `out` */,
                                         const srbd_lin_grad_f64* grad, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The two backward passes in one (additive to ABI 12): robot and plan gradients straight from the
+ * solve.  The ten outputs of grad are what
+ *   1. srbd_qp_solve_backward_rows_f64(h, batch, settings, data, sol, gx, gu, act_tol, rank_tol,
+ *      &all_nine, &rows, stream)
+ *   2. srbd_qp_srbd_linearize_backward_f64(h, batch, params, plan, constraints, xs, us,
+ *      cot = those arrays, grad, stream)
+ * return at the same act_tol, rank_tol and settings, and grad_x0 is the first call's grad x0; the
+ * gradients of A, B, Q, S, R and D are never formed.  Every block of them is two outer products
+ * of vectors the handle holds, so the linearisation's reverse model reads, for stage k < N, with
+ * pi+ = pi[k+1], dpi+ = dpi[k+1] and x, u, dx, du of stage k:
+ *   cot A_ij = pi+_i dx_j + dpi+_i x_j        cot B_ij = pi+_i du_j + dpi+_i u_j
+ *   cot R_ii = du_i u_i,  cot R_ij + cot R_ji = du_i u_j + u_i du_j      cot Q[k]_jj = dx_kj x_kj
+ *   cot q[k] = dx_k (k <= N)     cot r = du     cot b = dpi+     grad x0 = dpi[0]
+ *   CONE: cot D_jc = dnu_j u_c + nu_j du_c,  cot lg_j = -dnu_j  (nu, dnu: the multipliers of the
+ *         rows and of their adjoint; the cone's rows have no upper side, ug_mask = 0)
+ *   BOX_U: cot ubu_i = -dnu_i of an input pinned at its upper bound
+ * only where the linearisation depends on a robot's or a plan's value: 47 sums per stage.
+ * Modes and handle: SRBD_QP_SRBD_NONE, _BOX_U and _CONE with nx = nu = 12 in the QP-major layout.
+ * data is what srbd_qp_srbd_linearize[_plan]_f64 wrote at xs, us with the same params, plan and
+ * MODEL role, which are read as the linearisation reads them; sol is the forward x, u, pi.  x, u,
+ * pi, xs, us need only be 8-byte aligned.  An active set on the handle is not consulted.
+ * An output that is passed is fully written; a NULL one costs nothing.  The same inputs give the
+ * same bits.  srbd_qp_backward_active_f64 reports this call's counts.
+ * Checks, in this order, before any device work, with the codes and messages of the two calls:
+ *   1. those of srbd_qp_srbd_linearize_backward_f64: NULL h, params, xs, us or grad: SRBD_QP_EINVAL;
+ *      a handle without nx = nu = 12: SRBD_QP_EDIM; batch above the capacity: SRBD_QP_ECAPACITY;
+ *      unknown constraints, or CONE on a handle without ng = 24: SRBD_QP_EINVAL;
+ *   2. those of srbd_qp_solve_backward_rows_f64 on settings, data, sol, gx, gu, act_tol, rank_tol;
+ *   3. a grad whose fields are all NULL together with grad_x0 == NULL: SRBD_QP_EINVAL;
+ *   4. batch == 0: SRBD_QP_OK.
+ * A failed check launches and writes nothing.
+ * Buffers: the backward buffer of srbd_qp_solve_backward_rows_f64 and the scratch rows of
+ * srbd_qp_srbd_linearize_backward_f64, and between the lift kernel and the fused kernels a
+ * compact buffer of capacity N (2 ng + (has_box_u ? nu : 0)) doubles -- nu and dnu of the rows,
+ * the gradient of ubu -- allocated on first use (srbd_qp_memory_bytes counts it): 384 bytes per
+ * stage with the cone against the 2304 of grad D, nothing on a handle without constraints.
+ * Nothing of 144 or ng nu doubles per stage is written anywhere.
+ * Asynchronous on `stream` like the two calls, under the contract of srbd_qp_solve_backward_f64.
+ * Out of scope: gradients with respect to xs, us; the constants that are not per robot; the PLANT
+ * role, the advance and the rollouts; active sets; fp32 and the mixed-precision settings;
+ * srbd_qp_multi_* and the hpipm-cpp shim; state boxes, rows on the states and soft boxes
+ * (rejected with the codes of the two calls).
+ * ---------------------------------------------------------------------- */
+int srbd_qp_srbd_solve_backward_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
+                                    const srbd_model_params* params, const srbd_plan_f64* plan /* may be NULL */,
+                                    int constraints,
+                                    const double* xs, const double* us,  /* the linearisation point          */
+                                    const srbd_qp_data_f64* data,        /* what the linearisation wrote     */
+                                    const srbd_qp_solution_f64* sol,     /* the forward x, u, pi (read only) */
+                                    const double* gx, const double* gu,  /* cotangents; either may be NULL   */
+                                    double act_tol, double rank_tol,
+                                    const srbd_lin_grad_f64* grad,       /* the ten outputs, any may be NULL */
+                                    double* grad_x0,                     /* [batch][12] = dpi[0]; may be NULL */
+                                    void* stream);
 
 /* ------------------------------------------------------------------------
  * Gait planner (additive to ABI 12): the producer of a tick's plan window.  From a per-robot

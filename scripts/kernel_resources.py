@@ -2,17 +2,23 @@
 """Per-kernel VGPRs / scratch / occupancy of a HIP source (hipcc -Rpass-analysis).
 
 Usage: scripts/kernel_resources.py srbd-nmpc-solver_amd/csrc/ipm_box.hip [filter]
+       scripts/kernel_resources.py backward [filter]
+`backward`: the sources of the linearisation's two backward passes (DESIGN.md 4.13c, 4.13d:
+srbd_lin_bwd_*, srbd_solve_bwd_*) and of the lift kernel that feeds the fused one.
 """
 import re
 import subprocess
 import sys
 
-src = sys.argv[1]
+CSRC = "srbd-nmpc-solver_amd/csrc/"
+GROUPS = {"backward": [CSRC + "srbd_linearize_backward.hip", CSRC + "srbd_solve_backward.hip",
+                       CSRC + "qp_backward_rows.hip"]}
+srcs = GROUPS.get(sys.argv[1], [sys.argv[1]])
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
-out = subprocess.run(
+out = "".join(subprocess.run(
     ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", src,
      "-o", "/tmp/_kres.o", "-Rpass-analysis=kernel-resource-usage"],
-    capture_output=True, text=True).stderr
+    capture_output=True, text=True).stderr for src in srcs)
 cur = None
 rows = []
 for line in out.splitlines():

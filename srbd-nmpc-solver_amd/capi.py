@@ -482,6 +482,8 @@ def _prototypes():
         "srbd_qp_srbd_rollout_f64": (i, [h, i, mp, plan, ls, st, i, i, P(RolloutStruct)] + [vp] * 4, maybe),
         "srbd_qp_srbd_set_robots_f64": (i, [h, i, P(RobotsStruct)], maybe),
         "srbd_qp_srbd_linearize_backward_f64": (i, [h, i, mp, plan, i, vp, vp, d64, P(LinGrad), vp], maybe),
+        "srbd_qp_srbd_solve_backward_f64": (i, [h, i, st, mp, plan, i, vp, vp, d64, s64, vp, vp, C.c_double, C.c_double,
+                                                P(LinGrad), vp, vp], maybe),  # the fused backward pass
         "srbd_qp_srbd_set_terrain_f64": (i, [h, P(TerrainStruct)], maybe),
         "srbd_qp_srbd_terrain_height_f64": (i, [h, i] + [vp] * 4, maybe),
         "srbd_qp_srbd_set_contact_f64": (i, [h, P(ContactStruct)], maybe),
@@ -660,6 +662,25 @@ class Handle:
                                                 C.c_void_p(stream or None)), "srbd_qp_backward_active_f64")
         _order_after(o)
         return count
+
+    def srbd_solve_backward_device(self, batch: int, settings: Settings, params: "ModelParams", plan_ref,
+                                   constraints: int, xs, us, data: Data, sol: Solution, gx, gu, grad: LinGrad,
+                                   grad_x0=None, act_tol: float = 0.0, rank_tol: float = 1e-8, stream: int = 0,
+                                   order: bool = True) -> None:
+        """srbd_qp_srbd_solve_backward_f64: solve_backward_rows_device and the linearisation's
+        backward pass in one call -- the gradients of the robots' and the plan's values into the
+        non-NULL fields of `grad` and dpi[0] into grad_x0, from the cotangents gx, gu at the
+        forward solution `sol` of the QP `data` that srbd_linearize wrote at xs, us.  xs, us, gx,
+        gu, grad_x0: torch fp64 device tensors or device addresses; plan_ref: byref(PlanStruct) or
+        None; constraints: the mode's number (SRBD_CONSTRAINTS)."""
+        ptr = lambda t: C.c_void_p((t if isinstance(t, int) else _tensor_ptr(t)) or None)
+        o = _order_before(self, stream, order)
+        check(lib().srbd_qp_srbd_solve_backward_f64(self._h, int(batch), C.byref(settings), C.byref(params), plan_ref,
+                                                    int(constraints), ptr(xs), ptr(us), C.byref(data), C.byref(sol),
+                                                    ptr(gx), ptr(gu), float(act_tol), float(rank_tol), C.byref(grad),
+                                                    ptr(grad_x0), C.c_void_p(stream or None)),
+              "srbd_qp_srbd_solve_backward_f64")
+        _order_after(o)
 
     def solve_soft_host(self, batch: int, settings: Settings, data: Data, soft: Soft, sol: Solution,
                         slack: Optional[Slack] = None) -> None:
@@ -1053,6 +1074,53 @@ def srbd_linearize_backward(handle: Handle, xs, us, cot: Dict, constraints: str 
                                                     C.c_void_p(stream or None)),
           "srbd_qp_srbd_linearize_backward_f64")
     _order_after(o)
+    return res
+
+
+def srbd_solve_backward(handle: Handle, xs, us, data: Data, sol: Solution, gx, gu, constraints: str = "none",
+                        params: Optional[ModelParams] = None, plan: Optional[Plan] = None, act_tol: float = 0.0,
+                        rank_tol: float = 1e-8, want=LIN_GRAD_FIELDS, settings=None, want_x0: bool = False,
+                        stream: int = 0, out=None):
+    """srbd_qp_srbd_solve_backward_f64: srbd_linearize_backward's gradients straight from the solve --
+    what Handle.solve_backward_rows_device followed by srbd_linearize_backward returns, without the
+    gradients of the QP arrays in between.
+    data: the Data srbd_linearize returned at the same xs, us, constraints, params and plan (with
+    x0 set); sol: a Solution with the forward x, u, pi of the handle's solve of it; gx [B][N+1][12],
+    gu [B][N][12]: the cotangents (torch fp64 device tensors; either may be None = zero).  The
+    tensors behind data and sol stay the caller's to keep alive.
+    want: the outputs to form (LIN_GRAD_FIELDS; may be empty with want_x0); want_x0: also "x0"
+    [B][12], the gradient of the initial state; `out`: {name: tensor} to write into instead of
+    allocating.  settings: as for the forward solve (reg_prim and ric_alg are read).
+    Returns {name: tensor} in srbd_linearize_backward's shapes."""
+    import torch
+    if constraints not in SRBD_CONSTRAINTS:
+        raise ValueError(f"unknown constraints {constraints!r}")
+    _check_tensor("xs", xs, (torch.float64,), ("B", None, 12), None, any_gpu=True)
+    B, N = xs.shape[0], xs.shape[1] - 1
+    _check_tensor("us", us, (torch.float64,), (B, N, 12), xs.device)
+    for name, t, rows in (("gx", gx, N + 1), ("gu", gu, N)):
+        if t is not None:
+            _check_tensor(name, t, (torch.float64,), (B, rows, 12), xs.device)
+    want = tuple(want)
+    unknown = [n for n in want if n not in LIN_GRAD_FIELDS]
+    if unknown or not (want or want_x0):
+        raise ValueError(f"want must name outputs among {LIN_GRAD_FIELDS}, got {want}")
+    plan_ref = _plan_ref(plan, B, N, xs.device)
+    _check_rows(handle, B, "robots")
+    res = {}
+    for name in want + (("x0",) if want_x0 else ()):
+        shape = (B,) + ((12,) if name == "x0" else _lin_grad_shape(name, N))
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float64, device=xs.device)
+        else:
+            _check_tensor(f"out[{name!r}]", t, (torch.float64,), shape, xs.device)
+        res[name] = t
+    grad = LinGrad(**{n: res[n].data_ptr() for n in want})
+    st = settings if isinstance(settings, Settings) else settings_struct(settings)
+    handle.srbd_solve_backward_device(B, st, params or default_model_params(), plan_ref, SRBD_CONSTRAINTS[constraints],
+                                      xs, us, data, sol, gx, gu, grad, res.get("x0"), act_tol=act_tol,
+                                      rank_tol=rank_tol, stream=stream)
     return res
 
 

@@ -2,7 +2,9 @@
 // srbd_qp_solve_backward_f64, srbd_qp_backward_pinned_f64, and with general rows and the
 // gradients of D and the bounds srbd_qp_solve_backward_rows_f64, srbd_qp_backward_active_f64):
 // the checks of a call, the adjoint QP's launch arguments, the Riccati solve that is the adjoint,
-// and the gradient kernels (qp_backward.hip, qp_backward_rows.hip).
+// and the gradient kernels (qp_backward.hip, qp_backward_rows.hip).  The checks
+// and the front half of a call (counts, projection or mask, the adjoint solve) are functions of
+// their own, shared with srbd_qp_srbd_solve_backward_f64 (capi_srbd.hip).
 #include "capi_handle.h"
 #include "qp_backward.h"
 #include "qp_backward_rows.h"
@@ -48,13 +50,18 @@ struct BackwardLayout {
   }
 };
 
-int backward_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const srbd_qp_data_f64* d,
-                  const srbd_qp_solution_f64* s, const double* gx, const double* gu, double act_tol,
-                  const srbd_qp_grad_f64* g, void* stream, bool rows = false, double rank_tol = 0.0,
-                  const srbd_qp_grad_rows_f64* gr = nullptr) {
+}  // namespace
+
+namespace srbd {
+namespace capi {
+
+// The checks of a backward call, in the header's order, up to (not including) batch == 0.
+int backward_check(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const srbd_qp_data_f64* d,
+                   const srbd_qp_solution_f64* s, const double* gx, const double* gu, double act_tol, bool rows,
+                   double rank_tol, bool have_grad) {
   // the checks that read the arguments alone come first; the handle is read after them
   if (!h) return fail(SRBD_QP_EINVAL, "handle is NULL");
-  if (!d || !s || (!g && !gr)) return fail(SRBD_QP_EINVAL, "data/solution/grad is NULL");
+  if (!d || !s || !have_grad) return fail(SRBD_QP_EINVAL, "data/solution/grad is NULL");
   if (!st) return fail(SRBD_QP_EINVAL, "settings is NULL");
   if (!gx && !gu) return fail(SRBD_QP_EINVAL, "gx and gu are both NULL: no cotangent");
   if (!(act_tol >= 0.0) || !std::isfinite(act_tol))
@@ -79,10 +86,17 @@ int backward_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const
     return fail(SRBD_QP_EINVAL, "a handle with has_box_u needs lbu and ubu (the forward call's)");
   if (dm.ng > 0 && (!d->D || !d->lg || !d->ug))
     return fail(SRBD_QP_EINVAL, "a handle with ng > 0 needs D, lg and ug (the forward call's)");
-  if (batch == 0) return SRBD_QP_OK;
+  return SRBD_QP_OK;
+}
 
-  hipStream_t strm = stream_of(h, stream);
-  srbd::DeviceGuard guard(h->device);
+// The front half of a backward call that has passed its checks, batch > 0, on the handle's device:
+// the counts cleared, the stages projected or masked where an input or a row is active, and the
+// adjoint QP solved by launch_riccati_unconstr.  out: where the adjoint solution is, and the lift
+// kernel's arguments but for its outputs.
+int backward_adjoint(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const srbd_qp_data_f64* d,
+                     const srbd_qp_solution_f64* s, const double* gx, const double* gu, double act_tol, bool rows,
+                     double rank_tol, hipStream_t strm, BackwardAdjoint* out) {
+  const srbd_qp_dims& dm = h->dims;
   const BackwardLayout L(dm, (size_t)h->capacity, rows);
   const bool padded = dm.nx != 12 || dm.nu != 12;
   const void* before = h->bwd.p;
@@ -121,7 +135,8 @@ int backward_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const
   h->bwd_counted = 0;
   h->bwd_active = 0;
   // what the projection and the lift kernel share: the inputs the active set is a function of
-  srbd::BackwardRowsArgs ra{};
+  srbd::BackwardRowsArgs& ra = out->rows;
+  ra = srbd::BackwardRowsArgs{};
   if (rows) {
     ra.batch = batch;
     ra.N = dm.N;
@@ -185,13 +200,39 @@ int backward_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const
   if (e == hipSuccess && padded) e = srbd::pad_problem<double>(a, h->pad.as<double>(), run, strm);
   if (e == hipSuccess) e = srbd::launch_riccati_unconstr(run, strm);
   if (e == hipSuccess && padded) e = srbd::unpad_solution<double>(a, run, strm);
-  if (e == hipSuccess && gr) {
-    ra.x = s->x;
-    ra.pi = s->pi;
-    ra.r = d->r;
-    ra.dx = a.x;
-    ra.du = a.u;
-    ra.dpi = a.pi;
+  if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
+  out->dx = a.x;
+  out->du = a.u;
+  out->dpi = a.pi;
+  ra.x = s->x;
+  ra.pi = s->pi;
+  ra.r = d->r;
+  ra.dx = a.x;
+  ra.du = a.u;
+  ra.dpi = a.pi;
+  return SRBD_QP_OK;
+}
+
+}  // namespace capi
+}  // namespace srbd
+
+namespace {
+
+int backward_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const srbd_qp_data_f64* d,
+                  const srbd_qp_solution_f64* s, const double* gx, const double* gu, double act_tol,
+                  const srbd_qp_grad_f64* g, void* stream, bool rows = false, double rank_tol = 0.0,
+                  const srbd_qp_grad_rows_f64* gr = nullptr) {
+  if (const int rc = backward_check(h, batch, st, d, s, gx, gu, act_tol, rows, rank_tol, g || gr)) return rc;
+  if (batch == 0) return SRBD_QP_OK;
+
+  hipStream_t strm = stream_of(h, stream);
+  srbd::DeviceGuard guard(h->device);
+  const srbd_qp_dims& dm = h->dims;
+  BackwardAdjoint adj;
+  if (const int rc = backward_adjoint(h, batch, st, d, s, gx, gu, act_tol, rows, rank_tol, strm, &adj)) return rc;
+  hipError_t e = hipSuccess;
+  if (gr) {
+    srbd::BackwardRowsArgs& ra = adj.rows;
     ra.gD = gr->D;
     ra.glg = gr->lg;
     ra.gug = gr->ug;
@@ -208,9 +249,9 @@ int backward_impl(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const
     ga.x = s->x;
     ga.u = s->u;
     ga.pi = s->pi;
-    ga.dx = a.x;
-    ga.du = a.u;
-    ga.dpi = a.pi;
+    ga.dx = adj.dx;
+    ga.du = adj.du;
+    ga.dpi = adj.dpi;
     ga.A = g->A;
     ga.B = g->B;
     ga.b = g->b;

@@ -9,6 +9,7 @@
 #include "../../include/srbd_qp.h"
 #include "device_guard.h"
 #include "kernels.h"
+#include "qp_backward_rows.h"
 #include "qp_fields.h"
 
 #include <hip/hip_runtime.h>
@@ -103,10 +104,13 @@ struct srbd_qp_handle_s {
   int bwd_active = 0;
   // srbd_qp_srbd_linearize_backward_f64: the per-stage parts of the robots' sums (capacity QPs)
   srbd::Buffer lin_bwd;
+  // srbd_qp_srbd_solve_backward_f64: what the lift kernel hands to the fused stage kernel, per
+  // stage nu, dnu (2 ng doubles, ng > 0) and the gradient of ubu (nu doubles, has_box_u); capacity QPs
+  srbd::Buffer bwd_fused;
   template <typename F>
   void each_buffer(F&& f) {
     for (srbd::Buffer* b : {&stage, &pinned, &pad, &soft_ws, &soft_pad, &nmpc, &roll, &roll_plan, &resc, &resc2, &mixed,
-                            &lqsw, &bwd, &lin_bwd})
+                            &lqsw, &bwd, &lin_bwd, &bwd_fused})
       f(*b);
   }
   int* nmpc_active_host = nullptr;  // pinned
@@ -178,6 +182,21 @@ int validate_call(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const
 template <typename T, typename DataT, typename SolT>
 srbd::ProblemArgsT<T> build_args(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const DataT* d,
                                  const SolT* s, int* status, const T* warm_bars, int skip_last_rb);
+// capi_backward.hip: the checks of a backward call up to (not including) batch == 0 (rows: those of
+// srbd_qp_solve_backward_rows_f64; have_grad: an output struct was passed), and the front half the
+// backward entry points share -- counts, projection or mask, the adjoint Riccati solve -- for a
+// call that has passed them with batch > 0, on the handle's device.  rows: the lift kernel's
+// arguments with every output NULL.
+struct BackwardAdjoint {
+  const double *dx, *du, *dpi;
+  srbd::BackwardRowsArgs rows;
+};
+int backward_check(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const srbd_qp_data_f64* d,
+                   const srbd_qp_solution_f64* s, const double* gx, const double* gu, double act_tol, bool rows,
+                   double rank_tol, bool have_grad);
+int backward_adjoint(srbd_qp_handle h, int batch, const srbd_qp_settings* st, const srbd_qp_data_f64* d,
+                     const srbd_qp_solution_f64* s, const double* gx, const double* gu, double act_tol, bool rows,
+                     double rank_tol, hipStream_t strm, BackwardAdjoint* out);
 // capi_host.hip: stops the handle's resident server, if any; on the handle's device
 void server_stop(srbd_qp_handle h);
 

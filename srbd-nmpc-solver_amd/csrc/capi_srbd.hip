@@ -1,6 +1,6 @@
 // capi_srbd.hip -- the SRBD entry points of the C-ABI (include/srbd_qp.h, srbd_qp_srbd_*):
-// robots, terrain and the plant's contact model, linearisation, line search, the NMPC step, the plant step, the gait
-// planner and the closed-loop rollout.
+// robots, terrain and the plant's contact model, linearisation and its backward passes, line search, the NMPC
+// step, the plant step, the gait planner and the closed-loop rollout.
 #include "capi_handle.h"
 
 #include <cmath>
@@ -221,6 +221,68 @@ int srbd_qp_srbd_linearize_backward_f64(srbd_qp_handle h, int batch, const srbd_
   }
   const hipError_t e = srbd::launch_srbd_linearize_backward(p, batch, d.N, constraints, xs, us, *cot, g,
                                                             h->lin_bwd.as<double>(), strm, plan, &h->robots_model);
+  if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
+  return SRBD_QP_OK;
+}
+
+// The two backward passes in one: the linearisation's checks, then the solve's,
+// then the outputs; the front half of srbd_qp_solve_backward_rows_f64, the lift kernel into the
+// handle's compact rows, and the fused kernels that read the vectors where they are.
+int srbd_qp_srbd_solve_backward_f64(srbd_qp_handle h, int batch, const srbd_qp_settings* settings,
+                                    const srbd_model_params* params, const srbd_plan_f64* plan, int constraints,
+                                    const double* xs, const double* us, const srbd_qp_data_f64* data,
+                                    const srbd_qp_solution_f64* sol, const double* gx, const double* gu,
+                                    double act_tol, double rank_tol, const srbd_lin_grad_f64* grad,
+                                    double* grad_x0, void* stream) {
+  if (!h || !params || !xs || !us || !grad) return fail(SRBD_QP_EINVAL, "NULL argument");
+  const srbd_qp_dims& d = h->dims;
+  if (const int rc = check_srbd_call(h, batch, "SRBD linearisation needs nx = nu = 12")) return rc;
+  if (constraints < SRBD_QP_SRBD_NONE || constraints > SRBD_QP_SRBD_CONE)
+    return fail(SRBD_QP_EINVAL, "unknown constraints mode");
+  if (constraints == SRBD_QP_SRBD_CONE && d.ng != 24) return fail(SRBD_QP_EINVAL, "CONE needs ng = 24");
+  if (const int rc = backward_check(h, batch, settings, data, sol, gx, gu, act_tol, true, rank_tol, true)) return rc;
+  const srbd_lin_grad_f64& g = *grad;
+  const bool sums = g.mass || g.Lbody || g.mu || g.R;
+  if (!sums && !g.Q && !g.Qf && !g.x_ref && !g.foot_r && !g.foot_l && !g.fz_max && !grad_x0)
+    return fail(SRBD_QP_EINVAL, "srbd_solve_backward: every output of grad and grad_x0 are NULL");
+  if (batch == 0) return SRBD_QP_OK;
+  const srbd_model_params p = with_qf_scale(params, d.N);
+  hipStream_t strm = stream_of(h, stream);
+  srbd::DeviceGuard guard(h->device);
+  // the compact rows: nu, dnu of the cone's rows, then the gradient of ubu
+  const size_t stages = (size_t)h->capacity * (size_t)d.N;
+  const size_t row_elems = stages * (size_t)d.ng, box_elems = d.has_box_u ? stages * (size_t)d.nu : 0;
+  hipError_t e = hipSuccess;
+  if (sums) e = h->lin_bwd.reserve(srbd::lin_backward_part_elems(h->capacity, d.N) * sizeof(double));
+  if (e == hipSuccess) e = h->bwd_fused.reserve((2 * row_elems + box_elems) * sizeof(double));
+  if (e != hipSuccess) return hip_fail(alloc_code(e), "srbd_solve_backward scratch allocation failed: ", e);
+  BackwardAdjoint adj;
+  if (const int rc = backward_adjoint(h, batch, settings, data, sol, gx, gu, act_tol, true, rank_tol, strm, &adj))
+    return rc;
+  srbd::SolveBwdVecs v{};
+  v.x = sol->x;
+  v.u = sol->u;
+  v.pi = sol->pi;
+  v.dx = adj.dx;
+  v.du = adj.du;
+  v.dpi = adj.dpi;
+  v.gx0 = grad_x0;
+  double* const rows = h->bwd_fused.as<double>();
+  const bool stage_outputs = sums || g.foot_r || g.foot_l || g.fz_max;
+  if (stage_outputs && constraints == SRBD_QP_SRBD_CONE) {  // (ng = 24: checked)
+    adj.rows.nu_out = rows;
+    adj.rows.dnu_out = rows + row_elems;
+    v.nu = adj.rows.nu_out;
+    v.dnu = adj.rows.dnu_out;
+  }
+  if (stage_outputs && constraints == SRBD_QP_SRBD_BOX_U && d.has_box_u) {
+    adj.rows.gubu = rows + 2 * row_elems;
+    v.gubu = adj.rows.gubu;
+  }
+  e = srbd::launch_backward_lift(adj.rows, strm);  // (no output: no launch)
+  if (e == hipSuccess)
+    e = srbd::launch_srbd_solve_backward(p, batch, d.N, constraints, xs, us, v, g, h->lin_bwd.as<double>(), strm, plan,
+                                         &h->robots_model);
   if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
   return SRBD_QP_OK;
 }

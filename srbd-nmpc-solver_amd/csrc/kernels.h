@@ -271,6 +271,20 @@ hipError_t launch_srbd_linearize_backward(const srbd_model_params& p, int batch,
                                           const double* xs, const double* us, const srbd_qp_data_f64& cot,
                                           const srbd_lin_grad_f64& grad, double* part, hipStream_t stream,
                                           const srbd_plan_f64* plan, const srbd_robots_f64* robots);
+// srbd_solve_backward.hip (srbd_qp_srbd_solve_backward_f64): the same gradients straight from the
+// vectors of the solve and of its adjoint.  x, u, pi: the forward solution (8-byte aligned is
+// enough); dx, du, dpi: the adjoint's, 16-byte aligned; nu, dnu [batch][N][24]: the multipliers of
+// the cone's rows and of their adjoint (CONE; 0 where a row is inactive or dropped); gubu
+// [batch][N][12]: the gradient of ubu (BOX_U); either may be NULL (zero).  gx0 [batch][12]: out,
+// dpi[0], or NULL.  part as above.
+struct SolveBwdVecs {
+  const double *x, *u, *pi, *dx, *du, *dpi, *nu, *dnu, *gubu;
+  double* gx0;
+};
+hipError_t launch_srbd_solve_backward(const srbd_model_params& p, int batch, int N, int mode, const double* xs,
+                                      const double* us, const SolveBwdVecs& v, const srbd_lin_grad_f64& grad,
+                                      double* part, hipStream_t stream, const srbd_plan_f64* plan,
+                                      const srbd_robots_f64* robots);
 
 // srbd_rollout.hip: one tick's plant step and shift of the guess (srbd_qp_srbd_advance_f64).
 // The per-robot outputs carry a stride (doubles / ints per robot), so that the rollout writes

@@ -27,6 +27,10 @@ struct BackwardRowsArgs {
   // (any NULL: not formed; one that is passed is fully written, zeros included)
   const double *x, *pi, *r, *dx, *du, *dpi;
   double *gD, *glg, *gug, *glbu, *gubu;
+  // lift, internal (srbd_qp_srbd_solve_backward_f64): the multipliers of the general rows and of
+  // their adjoint as the kernel holds them, [batch][N][ng], 0 for an inactive or dropped row
+  // (NULL: not written)
+  double *nu_out, *dnu_out;
 };
 hipError_t launch_backward_project(const BackwardRowsArgs& a, hipStream_t stream);
 hipError_t launch_backward_lift(const BackwardRowsArgs& a, hipStream_t stream);

@@ -398,6 +398,23 @@ __global__ void __launch_bounds__(kThreads) backward_lift_kernel(BackwardRowsArg
       }
     }
   }
+  if (a.nu_out || a.dnu_out) {
+    if constexpr (kVec) {
+      double2* nuo = reinterpret_cast<double2*>(a.nu_out ? a.nu_out + blk0 * ng : nullptr);
+      double2* dnuo = reinterpret_cast<double2*>(a.dnu_out ? a.dnu_out + blk0 * ng : nullptr);
+      for (int l = tid; l < nb * (ng / 2); l += kThreads) {  // rows j, j + 1
+        const int lb = l / (ng / 2), j = 2 * (l - lb * (ng / 2));
+        if (nuo) nuo[l] = make_double2(snu[lb][j], snu[lb][j + 1]);
+        if (dnuo) dnuo[l] = make_double2(sdnu[lb][j], sdnu[lb][j + 1]);
+      }
+    } else {
+      for (int l = tid; l < nb * ng; l += kThreads) {
+        const int lb = l / ng, j = l - lb * ng;
+        if (a.nu_out) a.nu_out[blk0 * ng + l] = snu[lb][j];
+        if (a.dnu_out) a.dnu_out[blk0 * ng + l] = sdnu[lb][j];
+      }
+    }
+  }
   if (a.glg || a.gug) {
     for (int l = tid; l < nb * ng; l += kThreads) {
       const int lb = l / ng, j = l - lb * ng;
@@ -443,10 +460,10 @@ hipError_t launch_backward_project(const BackwardRowsArgs& a, hipStream_t stream
 }
 
 hipError_t launch_backward_lift(const BackwardRowsArgs& a, hipStream_t stream) {
-  if (a.batch <= 0 || !(a.gD || a.glg || a.gug || a.glbu || a.gubu)) return hipSuccess;
+  if (a.batch <= 0 || !(a.gD || a.glg || a.gug || a.glbu || a.gubu || a.nu_out || a.dnu_out)) return hipSuccess;
   const long long nblk = (long long)a.batch * a.N;
   const dim3 grid((unsigned)((nblk + kStages - 1) / kStages));
-  if (a.ng % 2 == 0 && aligned16({a.gD}))
+  if (a.ng % 2 == 0 && aligned16({a.gD, a.nu_out, a.dnu_out}))
     hipLaunchKernelGGL(backward_lift_kernel<true>, grid, dim3(kThreads), 0, stream, a);
   else
     hipLaunchKernelGGL(backward_lift_kernel<false>, grid, dim3(kThreads), 0, stream, a);

@@ -15,7 +15,13 @@ srbd_qp_srbd_linearize_backward_f64 backward), so that
     x, u, pi = solve_qp(handle, x0=x0, **{k: qp[k] for k in ("A", "B", "b", "Q", "S", "R", "q", "r")})
     loss(x, u).backward()        # robots.mass.grad, robots.Q.grad, plan.fz_max.grad, ...
 
-Both passes run the HIP kernels on the handle's device; nothing is computed by torch.
+srbd_solve is the two in one function with one backward call (srbd_qp_srbd_solve_backward_f64;
+DESIGN.md 4.13d): the gradients of the QP arrays are never formed or held.
+
+    x, u, pi = srbd_solve(handle, xs, us, x0, plan=plan)
+    loss(x, u).backward()        # robots.mass.grad, ..., plan.fz_max.grad, x0.grad
+
+All passes run the HIP kernels on the handle's device; nothing is computed by torch.
 """
 from __future__ import annotations
 
@@ -23,7 +29,7 @@ import math
 
 from . import capi
 
-__all__ = ["solve_qp", "srbd_linearize"]
+__all__ = ["solve_qp", "srbd_linearize", "srbd_solve"]
 
 _INPUTS = capi.GRAD_FIELDS  # A, B, b, Q, S, R, q, r, x0: the differentiable inputs, in this order
 _BOUNDS = ("lbu", "ubu", "lbu_mask", "ubu_mask")
@@ -229,3 +235,87 @@ def srbd_linearize(handle, xs, us, constraints="none", params=None, plan=None):
     leaves += [None if plan is None else getattr(plan, n) for n in _PLAN_FIELDS]
     outs = _linearize.apply(handle, constraints, params, plan, robots, xs, us, *leaves)
     return dict(zip(_LIN_OUT[constraints], outs))
+
+
+# ---- linearise and solve in one function, the fused backward pass ----
+# forward's arguments before the leaves: handle, constraints, params, plan, robots, settings, act_tol, rank_tol,
+# xs, us, x0 (x0 is differentiable: the last of the lead)
+_SOLVE_LEAD = 11
+
+
+def _make_srbd_solve():
+    import torch
+
+    class _SrbdSolve(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, handle, constraints, params, plan, robots, settings, act_tol, rank_tol, xs, us, x0, *leaves):
+            qp, data = capi.srbd_linearize(handle, xs, us, constraints, params=params, plan=plan)
+            data.x0 = x0.data_ptr()
+            batch, N = xs.shape[0], xs.shape[1] - 1
+            new = lambda rows: torch.zeros(batch, rows, 12, dtype=torch.float64, device=xs.device)
+            x, u, pi = new(N + 1), new(N), new(N + 1)
+            handle.solve_device(batch, settings, data, capi.Solution(x=x.data_ptr(), u=u.data_ptr(), pi=pi.data_ptr()))
+            ctx.handle, ctx.constraints, ctx.params, ctx.plan, ctx.robots = handle, constraints, params, plan, robots
+            ctx.settings, ctx.act_tol, ctx.rank_tol = settings, act_tol, rank_tol
+            ctx.qp = qp  # the QP arrays the backward pass reads: kept alive, not part of the graph
+            ctx.save_for_backward(xs, us, x0, x, u, pi)
+            ctx.mark_non_differentiable(pi)
+            return x, u, pi
+
+        @staticmethod
+        def backward(ctx, gx, gu, _gpi):
+            names = _ROBOT_FIELDS + _PLAN_FIELDS
+            none = (None,) * (_SOLVE_LEAD + len(names))
+            want = [n for n, need in zip(names, ctx.needs_input_grad[_SOLVE_LEAD:]) if need]
+            want_x0 = ctx.needs_input_grad[_SOLVE_LEAD - 1]
+            if (gx is None and gu is None) or not (want or want_x0):
+                return none
+            if getattr(ctx.handle, "_robots", (None, None))[0] is not ctx.robots:
+                raise RuntimeError("srbd_solve: the handle's model robots were replaced (Handle.set_robots) "
+                                   "between the forward and the backward pass")
+            xs, us, x0, x, u, pi = ctx.saved_tensors
+            data = capi.Data(**{k: capi._tensor_ptr(ctx.qp.get(k)) or None for k in capi.DATA_FIELDS})
+            data.x0 = x0.data_ptr()
+            sol = capi.Solution(x=x.data_ptr(), u=u.data_ptr(), pi=pi.data_ptr())
+            out = capi.srbd_solve_backward(ctx.handle, xs, us, data, sol, None if gx is None else gx.contiguous(),
+                                           None if gu is None else gu.contiguous(), ctx.constraints,
+                                           params=ctx.params, plan=ctx.plan, act_tol=ctx.act_tol,
+                                           rank_tol=ctx.rank_tol, want=want, settings=ctx.settings, want_x0=want_x0)
+            return none[:_SOLVE_LEAD - 1] + (out.get("x0"),) + tuple(out.get(n) for n in names)
+
+    return _SrbdSolve
+
+
+_srbd_solve = None
+
+
+def srbd_solve(handle, xs, us, x0, constraints="none", params=None, plan=None, settings=None, act_tol=None,
+               rank_tol=1e-8):
+    """srbd_linearize followed by solve_qp as one differentiable function with one backward call
+    (srbd_qp_srbd_solve_backward_f64): the SRBD linearisation at xs [B][N+1][12], us [B][N][12] solved
+    from x0 [B][12] on `handle` (created for the mode: has_box_u for "box_u", ng = 24 for "cone"),
+    returning (x, u, pi).
+    Gradients go to the leaves srbd_linearize finds -- the tensors of the handle's model robots
+    (mass, Lbody, mu, Q, Qf, R) and of `plan` (x_ref, foot_r, foot_l, fz_max) that require grad --
+    and to x0; xs and us get none.  The gradients of the QP arrays are never formed.  settings,
+    act_tol, rank_tol: as in solve_qp.  The backward pass raises RuntimeError if the handle's model
+    robots are no longer the Robots object the forward call saw."""
+    import torch
+    global _srbd_solve
+    if _srbd_solve is None:
+        _srbd_solve = _make_srbd_solve()
+    if constraints not in _LIN_OUT:
+        raise ValueError(f"unknown constraints {constraints!r}")
+    st = settings if isinstance(settings, capi.Settings) else capi.settings_struct(settings)
+    capi._check_tensor("xs", xs, (torch.float64,), ("B", None, 12), torch.device("cuda", handle.device), "the handle",
+                       any_gpu=True)
+    capi._check_tensor("x0", x0, (torch.float64,), (xs.shape[0], 12), xs.device)
+    if not (0.0 <= float(rank_tol) < 1.0):
+        raise ValueError("rank_tol must be in [0, 1)")
+    if act_tol is None:
+        act_tol = math.sqrt(st.tol_comp)
+    robots = getattr(handle, "_robots", (None, None))[0]
+    leaves = [None if robots is None else getattr(robots, n) for n in _ROBOT_FIELDS]
+    leaves += [None if plan is None else getattr(plan, n) for n in _PLAN_FIELDS]
+    return _srbd_solve.apply(handle, constraints, params, plan, robots, st, float(act_tol), float(rank_tol), xs, us,
+                             x0, *leaves)
