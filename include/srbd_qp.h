@@ -40,6 +40,8 @@
  *                                and the plan's values from the cotangents of the QP arrays.
  *   srbd_qp_srbd_solve_backward_f64  the same gradients straight from the solve and its adjoint:
  *                                the two backward passes in one, no QP gradient in between.
+ *   srbd_qp_srbd_plant_rollout_f64  the true robot alone: T ticks of the plant step from given
+ *                                inputs; srbd_qp_srbd_plant_rollout_backward_f64 is its adjoint.
  *   srbd_qp_srbd_gait_plan_f64   the producer of a tick's plan: a velocity command, a gait and
  *                                the measured state in, the window out (Raibert footholds).
  *   srbd_qp_srbd_rollout_gait_f64  the rollout that replans every tick.
@@ -869,6 +871,81 @@ int srbd_qp_srbd_solve_backward_f64(srbd_qp_handle h, int batch, const srbd_qp_s
                                     const srbd_lin_grad_f64* grad,       /* the ten outputs, any may be NULL */
                                     double* grad_x0,                     /* [batch][12] = dpi[0]; may be NULL */
                                     void* stream);
+
+/* ------------------------------------------------------------------------
+ * Differentiable plant (additive to ABI 12): the open-loop rollout of the true robot and its
+ * adjoint through time.  Nothing in the reference.  The forward call is the plant of the closed
+ * loop without the controller around it: the inputs are data (a rollout's u_log, for instance),
+ * so a logged trajectory can be replayed under other plant parameters, and the backward call
+ * gives the gradient of any trajectory loss with respect to the start, the inputs, the feet, the
+ * wrench, the mass and the inertia: what system identification from logs needs.
+ * Forward, per robot: x_traj[0] = x0, and x_traj[t+1] is x_traj[t] after `substeps` classical RK4
+ * steps of length dt / substeps of xdot = f(x, u[t]) + w[t], with f, the feet and w as in step 2
+ * of srbd_qp_srbd_advance_f64 (w adds wrench[t][0:3] to rows 3..5 and wrench[t][3:6] / mass to
+ * rows 9..11): the plant step of srbd_qp_srbd_advance_f64 without a contact model.  The input is
+ * applied as it is.  Host statement: srbd_model.py's plant_step, tick by tick.
+ * Mass and inertia are resolved per field as the plant step of srbd_qp_srbd_advance_f64 resolves
+ * them: the handle's PLANT role, else its MODEL role, else params.
+ * Neither call reads the handle's contact model, terrain or active set: they integrate the inputs
+ * they are given (a rollout's u_log already holds the projected inputs), and with any of the three
+ * set the results are the bits they are with it cleared.  So the frozen ticks of a fallen robot in
+ * a log are not reproduced (the plant keeps integrating), and the true-ground foot height of a
+ * contact model is the caller's to put into foot_r / foot_l.
+ * Backward: the outputs are the gradients of a loss l with d l / d x_traj = gx, all T + 1 rows
+ * (row 0 included: grad x0 = lambda_0 + gx[0]), by the adjoint recursion lambda_t = gx[t] +
+ * (d x_traj[t+1] / d x_traj[t])' lambda_(t+1) with every RK4 step reversed slope by slope; the
+ * substeps of a tick are recomputed from x_traj[t] (O(substeps^2) model evaluations per tick, no
+ * buffer).  grad mass and grad Lbody are per robot whether or not a role supplies the value; grad
+ * foot_r / foot_l have T dense rows whatever foot_stages is.  An output that is passed is fully
+ * written; a NULL one costs nothing; with every output NULL the call does nothing.  The sums run
+ * in a fixed order without atomics: the same inputs give the same bits, and an output has the
+ * bits it has when the others are asked for too.
+ * Both calls are asynchronous on `stream` (NULL = the handle's own stream), allocate no handle
+ * memory (srbd_qp_memory_bytes does not grow), and take device memory only.  x0, roll->u, x_traj
+ * and gx are accessed 16 bytes at a time and must be 16-byte aligned; the feet, the wrench and
+ * the outputs of grad need only be 8-byte aligned.
+ * Checks, in this order, before any device work:
+ *   1. SRBD_QP_EINVAL: a NULL h, params, roll or x0 (backward: h, params, roll); a NULL x_traj
+ *      (backward: also a NULL gx or grad); a NULL roll->u with ticks > 0; ticks < 0; substeps < 1;
+ *      foot_stages < 0 or 0 < foot_stages < ticks;
+ *   2. SRBD_QP_EDIM unless the handle has nx = nu = 12;
+ *   3. SRBD_QP_ECAPACITY for a batch above the capacity;
+ *   4. SRBD_QP_EINVAL for an x0, roll->u, x_traj or gx that is not 16-byte aligned;
+ *   5. batch == 0: SRBD_QP_OK.
+ * ticks == 0 writes x_traj[:, 0] = x0; the backward call then writes grad x0 = gx[:, 0] and
+ * zeros to grad mass and grad Lbody.  A failed check launches and writes nothing.
+ * Out of scope: the derivative of a contact model's projection, the gait rollout's internal
+ * feet, a tick-parallel adjoint for small batches, fp32, srbd_qp_multi_* and the hpipm-cpp shim.
+ * ---------------------------------------------------------------------- */
+typedef struct srbd_plant_rollout_f64 {
+  int ticks;            /* T >= 0 */
+  int substeps;         /* RK4 steps per tick, each dt / substeps; >= 1 (as srbd_advance_f64) */
+  int foot_stages;      /* rows per robot in foot_r / foot_l, >= T; 0 = T (a long plan's arrays pass as they are) */
+  const double* u;      /* [batch][T][12] the inputs, each held over its tick (a rollout's u_log) */
+  const double* foot_r; /* [batch][foot_stages][3], row t = the feet during tick t; NULL = params->foot_r */
+  const double* foot_l; /* the same for the left foot; NULL = params->foot_l */
+  const double* wrench; /* [batch][T][6], srbd_rollout_f64's layout; NULL = none */
+} srbd_plant_rollout_f64;
+
+int srbd_qp_srbd_plant_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                   const srbd_plant_rollout_f64* roll,
+                                   const double* x0 /*[batch][12]*/, double* x_traj /*[batch][T+1][12]*/,
+                                   void* stream);
+
+typedef struct srbd_plant_grad_f64 {  /* device, outputs; any may be NULL and then costs nothing */
+  double *x0;              /* [batch][12]    */
+  double *u;               /* [batch][T][12] */
+  double *foot_r, *foot_l; /* [batch][T][3] (dense T rows, whatever foot_stages is) */
+  double *wrench;          /* [batch][T][6]  */
+  double *mass;            /* [batch]        */
+  double *Lbody;           /* [batch][3]     */
+} srbd_plant_grad_f64;
+
+int srbd_qp_srbd_plant_rollout_backward_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                            const srbd_plant_rollout_f64* roll,
+                                            const double* x_traj /* the forward's output */,
+                                            const double* gx /*[batch][T+1][12] dl/dx_traj */,
+                                            const srbd_plant_grad_f64* grad, void* stream);
 
 /* ------------------------------------------------------------------------
  * Gait planner (additive to ABI 12): the producer of a tick's plan window.  From a per-robot

@@ -5,6 +5,7 @@ Usage: scripts/kernel_resources.py srbd-nmpc-solver_amd/csrc/ipm_box.hip [filter
        scripts/kernel_resources.py backward [filter]
 `backward`: the sources of the linearisation's two backward passes (DESIGN.md 4.13c, 4.13d:
 srbd_lin_bwd_*, srbd_solve_bwd_*) and of the lift kernel that feeds the fused one.
+`plant`: the open-loop plant rollout and its adjoint (srbd_plant_rollout_*).
 """
 import re
 import subprocess
@@ -12,7 +13,8 @@ import sys
 
 CSRC = "srbd-nmpc-solver_amd/csrc/"
 GROUPS = {"backward": [CSRC + "srbd_linearize_backward.hip", CSRC + "srbd_solve_backward.hip",
-                       CSRC + "qp_backward_rows.hip"]}
+                       CSRC + "qp_backward_rows.hip"],
+          "plant": [CSRC + "srbd_plant.hip"]}
 srcs = GROUPS.get(sys.argv[1], [sys.argv[1]])
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 out = "".join(subprocess.run(

@@ -376,6 +376,25 @@ class RolloutStruct(C.Structure):
                 ("converged_log", _dp)]
 
 
+class PlantRolloutStruct(C.Structure):
+    """srbd_plant_rollout_f64."""
+    _fields_ = [("ticks", C.c_int), ("substeps", C.c_int), ("foot_stages", C.c_int), ("u", _dp), ("foot_r", _dp),
+                ("foot_l", _dp), ("wrench", _dp)]
+
+
+PLANT_GRAD_FIELDS = ("x0", "u", "foot_r", "foot_l", "wrench", "mass", "Lbody")
+
+
+class PlantGrad(C.Structure):
+    """srbd_plant_grad_f64."""
+    _fields_ = [(n, _dp) for n in PLANT_GRAD_FIELDS]
+
+
+def _plant_grad_shape(name, T):
+    return {"x0": (12,), "u": (T, 12), "foot_r": (T, 3), "foot_l": (T, 3), "wrench": (T, 6), "mass": (),
+            "Lbody": (3,)}[name]
+
+
 class GaitStruct(C.Structure):
     """srbd_gait_f64."""
     _fields_ = [("period", C.c_int), ("swing", C.c_int * 2), ("offset", C.c_int * 2), ("period_r", _dp),
@@ -484,6 +503,9 @@ def _prototypes():
         "srbd_qp_srbd_linearize_backward_f64": (i, [h, i, mp, plan, i, vp, vp, d64, P(LinGrad), vp], maybe),
         "srbd_qp_srbd_solve_backward_f64": (i, [h, i, st, mp, plan, i, vp, vp, d64, s64, vp, vp, C.c_double, C.c_double,
                                                 P(LinGrad), vp, vp], maybe),  # the fused backward pass
+        "srbd_qp_srbd_plant_rollout_f64": (i, [h, i, mp, P(PlantRolloutStruct), vp, vp, vp], maybe),  # the plant
+        "srbd_qp_srbd_plant_rollout_backward_f64": (i, [h, i, mp, P(PlantRolloutStruct), vp, vp, P(PlantGrad), vp],
+                                                    maybe),
         "srbd_qp_srbd_set_terrain_f64": (i, [h, P(TerrainStruct)], maybe),
         "srbd_qp_srbd_terrain_height_f64": (i, [h, i] + [vp] * 4, maybe),
         "srbd_qp_srbd_set_contact_f64": (i, [h, P(ContactStruct)], maybe),
@@ -1215,6 +1237,95 @@ def srbd_advance(handle: Handle, xs, us, x=None, plan: Optional[Plan] = None, wr
           "srbd_qp_srbd_advance_f64")
     _order_after(o)
     return u0
+
+
+def _plant_roll(x0, u, foot_r, foot_l, wrench, substeps):
+    """The tensor checks srbd_plant_rollout and its backward call share: (B, T, PlantRolloutStruct).
+    x0 [B][12] names the device; u [B][T][12]; foot_r / foot_l [B][P][3] with one P >= T; wrench [B][T][6]."""
+    import torch
+    _check_tensor("x0", x0, (torch.float64,), ("B", 12), None, any_gpu=True)
+    B, dev = x0.shape[0], x0.device
+    _check_tensor("u", u, (torch.float64,), (B, None, 12), dev)
+    T = u.shape[1]
+    P = 0
+    for name, f in (("foot_r", foot_r), ("foot_l", foot_l)):
+        if f is None:
+            continue
+        _check_tensor(name, f, (torch.float64,), (B, None, 3), dev)
+        if f.shape[1] < T or (P and f.shape[1] != P):
+            raise ValueError(f"{name} has {f.shape[1]} rows per robot, expected "
+                             + (f"{P}, as the other foot" if P else f"at least the {T} ticks"))
+        P = f.shape[1]
+    if wrench is not None:
+        _check_f64("wrench", wrench, (B, T, 6), dev)
+    roll = PlantRolloutStruct(T, int(substeps), P, u.data_ptr() or None, _tensor_ptr(foot_r) or None,
+                              _tensor_ptr(foot_l) or None, _tensor_ptr(wrench) or None)
+    return B, T, roll
+
+
+def srbd_plant_rollout(handle: Handle, x0, u, foot_r=None, foot_l=None, wrench=None, substeps: int = 1,
+                       params: Optional[ModelParams] = None, stream: int = 0, out=None):
+    """The open-loop plant rollout (srbd_qp_srbd_plant_rollout_f64): x_traj [B][T+1][12] with
+    x_traj[:, 0] = x0 [B][12] and x_traj[:, t+1] the plant state after tick t -- `substeps` RK4 steps
+    of dt / substeps with the input u[:, t] (u [B][T][12], e.g. a rollout's u_log), the feet of row
+    t of foot_r / foot_l [B][P][3] (P >= T; None: params') and wrench[:, t] (wrench [B][T][6]; None:
+    none).  Mass and inertia are the handle's PLANT role's, else its MODEL role's, else params'.
+    The handle's contact, terrain and active set are not read.  Torch fp64 device tensors, 16-byte
+    aligned (x0, u, out); `out`: a tensor to write into.  Asynchronous on the handle's stream,
+    ordered like a torch op."""
+    import torch
+    B, T, roll = _plant_roll(x0, u, foot_r, foot_l, wrench, substeps)
+    _check_rows(handle, B, "robots")
+    if out is None:
+        out = torch.empty(B, T + 1, 12, dtype=torch.float64, device=x0.device)
+    else:
+        _check_f64("out", out, (B, T + 1, 12), x0.device)
+    p = params or default_model_params()
+    o = _order_before(handle, stream, True)
+    check(lib().srbd_qp_srbd_plant_rollout_f64(handle.ptr, int(B), C.byref(p), C.byref(roll),
+                                               C.c_void_p(x0.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(stream or None)), "srbd_qp_srbd_plant_rollout_f64")
+    _order_after(o)
+    return out
+
+
+def srbd_plant_rollout_backward(handle: Handle, x0, u, foot_r=None, foot_l=None, wrench=None, substeps: int = 1,
+                                params: Optional[ModelParams] = None, *, x_traj, gx, want=PLANT_GRAD_FIELDS,
+                                stream: int = 0, out=None):
+    """The adjoint of srbd_plant_rollout (srbd_qp_srbd_plant_rollout_backward_f64) at the same
+    arguments: x_traj what it returned, gx [B][T+1][12] the cotangent of x_traj (row 0 included).
+    want: the outputs to form (PLANT_GRAD_FIELDS); `out`: {name: tensor} to write into instead of
+    allocating.  mass and Lbody are per robot whether or not a role supplies the value.
+    Returns {name: tensor}: x0 [B][12], u [B][T][12], foot_r, foot_l [B][T][3], wrench [B][T][6],
+    mass [B], Lbody [B][3].  Asynchronous on the handle's stream, ordered like a torch op."""
+    import torch
+    B, T, roll = _plant_roll(x0, u, foot_r, foot_l, wrench, substeps)
+    dev = x0.device
+    _check_f64("x_traj", x_traj, (B, T + 1, 12), dev)
+    _check_f64("gx", gx, (B, T + 1, 12), dev)
+    want = tuple(want)
+    unknown = [n for n in want if n not in PLANT_GRAD_FIELDS]
+    if unknown or not want:
+        raise ValueError(f"want must name outputs among {PLANT_GRAD_FIELDS}, got {want}")
+    _check_rows(handle, B, "robots")
+    res = {}
+    for name in want:
+        shape = (B,) + _plant_grad_shape(name, T)
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float64, device=dev)
+        else:
+            _check_tensor(f"out[{name!r}]", t, (torch.float64,), shape, dev)
+        res[name] = t
+    grad = PlantGrad(**{n: t.data_ptr() or None for n, t in res.items()})
+    p = params or default_model_params()
+    o = _order_before(handle, stream, True)
+    check(lib().srbd_qp_srbd_plant_rollout_backward_f64(handle.ptr, int(B), C.byref(p), C.byref(roll),
+                                                        C.c_void_p(x_traj.data_ptr()), C.c_void_p(gx.data_ptr()),
+                                                        C.byref(grad), C.c_void_p(stream or None)),
+          "srbd_qp_srbd_plant_rollout_backward_f64")
+    _order_after(o)
+    return res
 
 
 def _rollout_logs(B, T, plan_stages, dev, wrench, substeps, alpha_reset):

@@ -1,6 +1,6 @@
 // capi_srbd.hip -- the SRBD entry points of the C-ABI (include/srbd_qp.h, srbd_qp_srbd_*):
 // robots, terrain and the plant's contact model, linearisation and its backward passes, line search, the NMPC
-// step, the plant step, the gait planner and the closed-loop rollout.
+// step, the plant step, the gait planner, the closed-loop rollout, and the open-loop plant rollout with its adjoint.
 #include "capi_handle.h"
 
 #include <cmath>
@@ -725,6 +725,69 @@ int srbd_qp_srbd_rollout_gait_f64(srbd_qp_handle h, int batch, const srbd_model_
   if (!gait || !gio) return fail(SRBD_QP_EINVAL, "NULL argument");
   return rollout_impl(h, batch, params, nullptr, gait, gio, ls, settings, constraints, sqp_max_loop, roll, xs,
                       us, x, alpha);
+}
+
+}  // extern "C"
+
+// ---- the differentiable plant: the open-loop rollout and its adjoint ----
+namespace {
+// the checks both calls make of `roll`, after their NULL arguments
+int check_plant_roll(const srbd_plant_rollout_f64* roll) {
+  if (!roll->u && roll->ticks > 0) return fail(SRBD_QP_EINVAL, "plant_rollout: roll->u is NULL");
+  if (roll->ticks < 0) return fail(SRBD_QP_EINVAL, "plant_rollout: ticks must be non-negative");
+  if (roll->substeps < 1) return fail(SRBD_QP_EINVAL, "plant_rollout: substeps must be at least 1");
+  if (roll->foot_stages < 0 || (roll->foot_stages > 0 && roll->foot_stages < roll->ticks))
+    return fail(SRBD_QP_EINVAL, "plant_rollout: foot_stages must be 0 or at least ticks");
+  return SRBD_QP_OK;
+}
+// mass and Lbody as the advance launcher resolves them for the plant: the PLANT role's, else the
+// MODEL role's, else NULL (params')
+void plant_robot(srbd_qp_handle h, const double** mass, const double** Lbody) {
+  *mass = h->robots_plant.mass ? h->robots_plant.mass : h->robots_model.mass;
+  *Lbody = h->robots_plant.Lbody ? h->robots_plant.Lbody : h->robots_model.Lbody;
+}
+}  // namespace
+
+extern "C" {
+
+int srbd_qp_srbd_plant_rollout_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                   const srbd_plant_rollout_f64* roll, const double* x0, double* x_traj,
+                                   void* stream) {
+  if (!h || !params || !roll || !x0) return fail(SRBD_QP_EINVAL, "NULL argument");
+  if (!x_traj) return fail(SRBD_QP_EINVAL, "plant_rollout: x_traj is NULL");
+  if (const int rc = check_plant_roll(roll)) return rc;
+  if (const int rc = check_srbd_call(h, batch, "the SRBD plant rollout needs nx = nu = 12")) return rc;
+  if (!aligned16(x0) || !aligned16(roll->u) || !aligned16(x_traj))
+    return fail(SRBD_QP_EINVAL, "plant_rollout: x0 / u / x_traj must be 16-byte aligned");
+  if (batch == 0) return SRBD_QP_OK;
+  hipStream_t strm = stream_of(h, stream);
+  srbd::DeviceGuard guard(h->device);
+  const double *mass, *Lbody;
+  plant_robot(h, &mass, &Lbody);
+  const hipError_t e = srbd::launch_srbd_plant_rollout(*params, batch, *roll, mass, Lbody, x0, x_traj, strm);
+  if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
+  return SRBD_QP_OK;
+}
+
+int srbd_qp_srbd_plant_rollout_backward_f64(srbd_qp_handle h, int batch, const srbd_model_params* params,
+                                            const srbd_plant_rollout_f64* roll, const double* x_traj,
+                                            const double* gx, const srbd_plant_grad_f64* grad, void* stream) {
+  if (!h || !params || !roll) return fail(SRBD_QP_EINVAL, "NULL argument");
+  if (!x_traj) return fail(SRBD_QP_EINVAL, "plant_rollout_backward: x_traj is NULL");
+  if (!gx || !grad) return fail(SRBD_QP_EINVAL, "plant_rollout_backward: gx or grad is NULL");
+  if (const int rc = check_plant_roll(roll)) return rc;
+  if (const int rc = check_srbd_call(h, batch, "the SRBD plant rollout needs nx = nu = 12")) return rc;
+  if (!aligned16(roll->u) || !aligned16(x_traj) || !aligned16(gx))
+    return fail(SRBD_QP_EINVAL, "plant_rollout_backward: u / x_traj / gx must be 16-byte aligned");
+  if (batch == 0) return SRBD_QP_OK;
+  hipStream_t strm = stream_of(h, stream);
+  srbd::DeviceGuard guard(h->device);
+  const double *mass, *Lbody;
+  plant_robot(h, &mass, &Lbody);
+  const hipError_t e =
+      srbd::launch_srbd_plant_rollout_backward(*params, batch, *roll, mass, Lbody, x_traj, gx, *grad, strm);
+  if (e != hipSuccess) return hip_fail(SRBD_QP_EDEVICE, "kernel launch: ", e);
+  return SRBD_QP_OK;
 }
 
 }  // extern "C"

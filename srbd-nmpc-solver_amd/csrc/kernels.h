@@ -324,6 +324,18 @@ struct RolloutRow {
 hipError_t launch_rollout_rows(int batch, const RolloutRow* rows, int nrows, double* alpha,
                                double alpha_value, hipStream_t stream);
 
+// srbd_plant.hip: the open-loop plant rollout (srbd_qp_srbd_plant_rollout_f64) and its adjoint
+// through time (srbd_qp_srbd_plant_rollout_backward_f64), one thread per robot.  mass [batch],
+// Lbody [batch][3]: what the plant step resolves to (the PLANT role's, else the MODEL role's);
+// NULL: p's.  x0, roll.u, x_traj and gx are read or written 16 bytes at a time.
+hipError_t launch_srbd_plant_rollout(const srbd_model_params& p, int batch, const srbd_plant_rollout_f64& roll,
+                                     const double* mass, const double* Lbody, const double* x0, double* x_traj,
+                                     hipStream_t stream);
+hipError_t launch_srbd_plant_rollout_backward(const srbd_model_params& p, int batch,
+                                              const srbd_plant_rollout_f64& roll, const double* mass,
+                                              const double* Lbody, const double* x_traj, const double* gx,
+                                              const srbd_plant_grad_f64& grad, hipStream_t stream);
+
 // srbd_gait.hip: one tick's plan window from a gait, a command and the measured state
 // (srbd_qp_srbd_gait_plan_f64).  The command carries a stride (doubles per robot), and the
 // optional logs receive row 0 of the feet / fz_max at robot r's log + r * stride, so that the

@@ -21,6 +21,13 @@ DESIGN.md 4.13d): the gradients of the QP arrays are never formed or held.
     x, u, pi = srbd_solve(handle, xs, us, x0, plan=plan)
     loss(x, u).backward()        # robots.mass.grad, ..., plan.fz_max.grad, x0.grad
 
+plant_rollout is the true robot's side: the open-loop plant rollout as a differentiable function of
+its start, inputs, feet and wrench and of the plant's mass and inertia (srbd_qp_srbd_plant_rollout_f64
+forward, srbd_qp_srbd_plant_rollout_backward_f64 backward).
+
+    x_traj = plant_rollout(handle, x0, u_log, foot_r, foot_l, wrench)
+    ((x_traj - x_log) ** 2).sum().backward()   # plant.mass.grad, plant.Lbody.grad, u_log.grad, ...
+
 All passes run the HIP kernels on the handle's device; nothing is computed by torch.
 """
 from __future__ import annotations
@@ -29,7 +36,7 @@ import math
 
 from . import capi
 
-__all__ = ["solve_qp", "srbd_linearize", "srbd_solve"]
+__all__ = ["solve_qp", "srbd_linearize", "srbd_solve", "plant_rollout"]
 
 _INPUTS = capi.GRAD_FIELDS  # A, B, b, Q, S, R, q, r, x0: the differentiable inputs, in this order
 _BOUNDS = ("lbu", "ubu", "lbu_mask", "ubu_mask")
@@ -319,3 +326,67 @@ def srbd_solve(handle, xs, us, x0, constraints="none", params=None, plan=None, s
     leaves += [None if plan is None else getattr(plan, n) for n in _PLAN_FIELDS]
     return _srbd_solve.apply(handle, constraints, params, plan, robots, st, float(act_tol), float(rank_tol), xs, us,
                              x0, *leaves)
+
+
+# ---- the plant: the open-loop rollout and its adjoint through time ----
+# forward's arguments before the tensors: handle, params, substeps, roles
+_PLANT_LEAD = 4
+_PLANT_TENSORS = ("x0", "u", "foot_r", "foot_l", "wrench", "mass", "Lbody")  # capi.PLANT_GRAD_FIELDS' order
+
+
+def _make_plant_rollout():
+    import torch
+
+    class _PlantRollout(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, handle, params, substeps, roles, x0, u, foot_r, foot_l, wrench, _mass, _Lbody):
+            x_traj = capi.srbd_plant_rollout(handle, x0, u, foot_r, foot_l, wrench, substeps, params)
+            ctx.handle, ctx.params, ctx.substeps, ctx.roles = handle, params, substeps, roles
+            ctx.given = tuple(t is not None for t in (foot_r, foot_l, wrench))
+            ctx.save_for_backward(x0, u, x_traj, *[t for t in (foot_r, foot_l, wrench) if t is not None])
+            return x_traj
+
+        @staticmethod
+        def backward(ctx, gx):
+            none = (None,) * (_PLANT_LEAD + len(_PLANT_TENSORS))
+            want = [n for n, need in zip(_PLANT_TENSORS, ctx.needs_input_grad[_PLANT_LEAD:]) if need]
+            if gx is None or not want:
+                return none
+            if getattr(ctx.handle, "_robots", (None, None)) != ctx.roles:
+                raise RuntimeError("plant_rollout: the handle's robots were replaced (Handle.set_robots) between the "
+                                   "forward and the backward pass")
+            x0, u, x_traj, *rest = ctx.saved_tensors
+            rest = iter(rest)
+            foot_r, foot_l, wrench = (next(rest) if g else None for g in ctx.given)
+            out = capi.srbd_plant_rollout_backward(ctx.handle, x0, u, foot_r, foot_l, wrench, ctx.substeps, ctx.params,
+                                                   x_traj=x_traj, gx=gx.contiguous(), want=want)
+            for name, foot in (("foot_r", foot_r), ("foot_l", foot_l)):  # a long plan's rows past T: zeros
+                if name in out and foot.shape[1] > u.shape[1]:
+                    full = torch.zeros_like(foot)
+                    full[:, :u.shape[1]] = out[name]
+                    out[name] = full
+            return none[:_PLANT_LEAD] + tuple(out.get(n) for n in _PLANT_TENSORS)
+
+    return _PlantRollout
+
+
+_plant_rollout = None
+
+
+def plant_rollout(handle, x0, u, foot_r=None, foot_l=None, wrench=None, substeps=1, params=None):
+    """capi.srbd_plant_rollout as a differentiable function: x_traj [B][T+1][12], the true robot's
+    states from x0 [B][12] under the inputs u [B][T][12], the feet foot_r / foot_l [B][P][3] (P >= T)
+    and the wrench [B][T][6], each held over its tick.
+    Gradients go to x0, u, foot_r, foot_l, wrench and to the mass / Lbody tensors the plant step
+    resolves to -- per field the handle's plant robots' (Handle.set_robots), else its model robots'
+    -- where they require grad; a foot tensor longer than T gets zeros in its rows past T.  The
+    backward pass raises RuntimeError if either role is no longer the Robots object the forward
+    call saw."""
+    global _plant_rollout
+    if _plant_rollout is None:
+        _plant_rollout = _make_plant_rollout()
+    roles = tuple(getattr(handle, "_robots", (None, None)))
+    model, plant = roles
+    leaf = lambda n: next((getattr(r, n) for r in (plant, model) if r is not None and getattr(r, n) is not None), None)
+    return _plant_rollout.apply(handle, params, int(substeps), roles, x0, u, foot_r, foot_l, wrench, leaf("mass"),
+                                leaf("Lbody"))
